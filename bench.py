@@ -16,7 +16,14 @@ counts m.  steps/s is reported beside it.
 The EKF path does not shard (one dense coupled covariance): with --gpus N > 1 every rank runs
 an independent replica on its own GPU ("replicas only", weak scaling, no data-path collective).
 
-Prints ONE JSON line (rank 0).
+Prints ONE JSON line (rank 0).  A plain run does what the headline needs and nothing else: set-up, device warm-up, the
+W warm-up steps, the K timed steps, the line (metric, value, unit, ms_per_step, ...).  Everything measured beside it --
+per-kernel times, the roofline (with its rocprofv3 --pmc traffic passes), predict / add_features, the copy floor, the CPU
+baselines, the C2 / C5 configurations, the FastSLAM leg -- runs with --full only.
+
+--dump-outputs DIR writes what the timed path's caller holds after the last timed step (the association vector and the
+state x, P; P through a fixed, seeded sample) as DIR/<name>.npy.  The inputs depend on the arguments only: the state the
+device warm-up changed is reset before the W warm-up steps.
 """
 from __future__ import annotations
 
@@ -63,10 +70,10 @@ def make_workload(N, nz, nsteps, seed):
     return x, P, zs
 
 
-def make_workload_on_device(pkg, N, nz, nsteps, seed, dtype, device):
+def make_workload_on_device(pkg, N, nz, nsteps, seed, dtype, device, st=None):
     """The same kind of workload for maps whose covariance does not fit the host comfortably (N = 50k, fp64:
     80 GB): x and the observations come from NumPy, P = A A' + 0.01 I is formed on the GPU by torch and handed to
-    the library device-to-device (slam_ekf_set_state_device)."""
+    the library device-to-device (slam_ekf_set_state_device).  With `st`, that handle's state is set (again)."""
     import torch
     rng = np.random.default_rng(seed)
     n = 3 + 2 * N
@@ -83,7 +90,8 @@ def make_workload_on_device(pkg, N, nz, nsteps, seed, dtype, device):
     Pd.diagonal().add_(0.01)
     Pd = torch.maximum(Pd, Pd.t()) if n <= 30000 else Pd
     xd = torch.from_numpy(x).to(dev)
-    st = pkg.EKFSlamState(np.asarray(x[:3]), np.zeros((3, 3), dtype=npdt), dtype=dtype, max_landmarks=N, device=device)
+    if st is None:
+        st = pkg.EKFSlamState(np.asarray(x[:3]), np.zeros((3, 3), dtype=npdt), dtype=dtype, max_landmarks=N, device=device)
     torch.cuda.synchronize(dev)
     st.set_state_device(xd.data_ptr(), Pd.data_ptr(), n, n)     # row-major == column-major for a symmetric matrix
     st.sync()
@@ -512,7 +520,7 @@ def measure_traffic(args, want_fastslam, landmarks=None, obs=None, dtype=None, f
         return {"error": "rocprofv3 not found"}
     names = {"downdate_f32_mfma": "downdate", "downdate_f64_mfma": "downdate", "pf_auto_step_kernel": "pf_step"}
     out = {}
-    child = [sys.executable, os.path.abspath(__file__), "--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--no-pmc", "--no-configs",
+    child = [sys.executable, os.path.abspath(__file__), "--full", "--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--no-pmc", "--no-configs",
              "--prewarm-ms", "20", "--landmarks", str(landmarks or args.landmarks), "--obs", str(obs or args.obs),
              "--dtype", dtype or args.dtype, "--form", form or args.form] + ([] if want_fastslam else ["--no-fastslam"])
     for counter, key in (("FETCH_SIZE", "fetch_kb"), ("WRITE_SIZE", "write_kb")):
@@ -728,6 +736,26 @@ def configs_guarded(pkg, steps, warmup, local_rank, pmc_by_cfg, budget_s=150.0):
     return res
 
 
+DUMP_COLUMNS_BYTES = 32 << 20          # --dump-outputs: the sampled columns of P stay below this
+
+
+def dump_outputs(d, st, assoc):
+    """--dump-outputs DIR: what a caller of the timed path holds after its last step -- the association vector
+    slam_ekf_observe returned and the state (x, P) -- as DIR/<name>.npy in the state's dtype (assoc as float64).  P (n x n,
+    1.6 GB at the headline) is represented by its diagonal, the three pose rows and whole columns at a fixed, seeded
+    sample of column indices (P_column_ids), together far below 64 MB."""
+    os.makedirs(d, exist_ok=True)
+    x = st.download("x")
+    n = x.shape[0]
+    ncol = max(1, min(256, n, DUMP_COLUMNS_BYTES // (n * x.dtype.itemsize)))
+    cols = np.sort(np.random.default_rng(SEED).choice(n, ncol, replace=False))
+    arrays = {"assoc": np.asarray(assoc, dtype=np.float64), "x": x, "P_diag": st.diag(), "P_pose_rows": st.get_block(0, 0, 3, n),
+              "P_column_ids": cols.astype(np.float64),
+              "P_columns": np.stack([st.get_block(0, int(c), n, 1)[:, 0] for c in cols], axis=1)}
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a))
+
+
 def spawn_ranks(n):
     """One child process per rank with RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set, the same command line; children
     are plain subprocesses (never an exec of this process).  Returns the exit code for the parent."""
@@ -773,6 +801,12 @@ def main():
     ap.add_argument("--dtype", default="f32", choices=["f32", "f64"])
     ap.add_argument("--form", default="cholesky", choices=["cholesky", "joseph"])
     ap.add_argument("--unfused", action="store_true", help="three library calls per step instead of slam_ekf_observe")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what stands beside the headline: per-kernel times, roofline (+ rocprofv3 --pmc traffic), "
+                         "predict / add_features, copy floor, CPU baselines, the C2 / C5 configurations, the FastSLAM leg; "
+                         "the --no-* options below select among these")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the timed path computed in its last step to DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-fastslam", action="store_true")
     ap.add_argument("--no-configs", action="store_true", help="skip the C2 / C5 sub-benchmarks (`configs` in the line)")
@@ -794,10 +828,10 @@ def main():
     under_profiler = "rocprof" in os.environ.get("LD_PRELOAD", "") or any(k.startswith(("ROCPROF", "ROCP_")) for k in os.environ)
     if under_profiler:                 # (the profiler's library has initialised the GPU already: no child processes from here)
         pmc = {"error": "this run is itself under rocprofv3"}
-    elif not args.no_pmc and "WORLD_SIZE" not in os.environ and args.gpus == 1:
+    elif args.full and not args.no_pmc and "WORLD_SIZE" not in os.environ and args.gpus == 1:
         pmc = measure_traffic(args, not args.no_fastslam)
     headline_cfg = args.landmarks == 10000 and args.obs == 64 and args.dtype == "f32" and args.form == "cholesky"
-    want_configs = headline_cfg and not args.no_configs and "WORLD_SIZE" not in os.environ and args.gpus == 1
+    want_configs = args.full and headline_cfg and not args.no_configs and "WORLD_SIZE" not in os.environ and args.gpus == 1
     pmc_cfg = {}
     if want_configs and pmc is not None and "error" not in pmc and not args.no_pmc:
         for cfg in OTHER_CONFIGS:                                 # (each configuration's own two --pmc child passes, still before this process touches the GPU)
@@ -846,8 +880,18 @@ def main():
                 st.add_features(z[:, a < 0], R)
         else:                              # the same step as ONE library call (slam_ekf_observe)
             a = st.observe(z, R, GATE1, GATE2, form=args.form)
+        last_assoc[0] = a
         return int((a > 0).sum())
 
+    last_assoc = [None]                    # what the last step returned (--dump-outputs)
+    # the device warm-up below runs for a fixed TIME, i.e. a varying number of state-changing steps: the state is reset to
+    # the workload's afterwards (from this device copy; the big covariance is formed again), so that the W warm-up and the
+    # K timed steps see the same inputs in every run with the same arguments
+    snap = None
+    if args.prewarm_ms > 0 and not big:
+        dev = torch.device("cuda", local_rank)
+        snap = (torch.from_numpy(np.ascontiguousarray(x, dtype=st.np_dtype)).to(dev),
+                torch.from_numpy(np.ascontiguousarray(P, dtype=st.np_dtype)).to(dev))     # symmetric: row-major = column-major
     st.set_async(True)                     # the update's status is collected at the final sync
     # The cyclic garbage collector is parked from here to the end of the timed region: a full collection of the
     # interpreter's ~10^5 objects (torch is imported) takes 40 ms, lands deterministically on one step
@@ -867,6 +911,12 @@ def main():
             if prewarm_steps % 16 == 0:
                 st.sync()
         st.sync()
+        if big:
+            make_workload_on_device(pkg, N, nz, total_steps, SEED + rank, args.dtype, local_rank, st=st)
+        else:
+            torch.cuda.synchronize()
+            st.set_state_device(snap[0].data_ptr(), snap[1].data_ptr(), n, n)
+            snap = None
     for i in range(args.warmup):
         step(zs[i])
     st.sync()
@@ -898,52 +948,55 @@ def main():
     elapsed = time.perf_counter() - t0
     gc.enable()
 
-    tim = st.timing_read()
-    syrk_min_ms = st.timing_min("syrk")
-    # diagnostics (outside the timed region): every kernel bracketed, and the factorisation kernel's phase stamps
-    ndiag = min(5, total_steps)
-    st.timing(True)
-    st.timing_reset()
-    for i in range(ndiag):
-        step(zs[total_steps - 1 - i])
-    st.sync()
-    tim_all = st.timing_read()
-    st.timing(False)
-    # the timed region brackets every 4th of its steps (5 launches at the driver's 20 steps: a mean whose +-2 % is
-    # the size of a round's gain).  NROOF more steps of the same kind with the down-date bracketed on every one: roofline.frac is
-    # formed from THIS mean; the timed region's stays beside it as avg_launch_ms.
-    st.timing(True, kernels=["syrk"])
-    st.timing_reset()
-    rng_rf = np.random.default_rng(SEED + 104729 + rank)
-    matched_roof = 0
-    for i in range(NROOF):
-        matched_roof += step(zs[(args.warmup + i) % total_steps] + rng_rf.normal(0, 1, zs[0].shape) * np.array([[0.02], [0.2 * math.pi / 180]]))
-    st.sync()
-    roof_n, roof_mean_ms, roof_sd_ms, roof_min_ms = st.timing_stats("syrk")
-    st.timing(False)
-    st.debug_stamps(True)
-    step(zs[-1])
-    st.sync()
-    stamps = st.debug_stamps(False)
-    phases = [(b - a) / 100.0 for a, b in zip(stamps[:6], stamps[1:7])]     # 100 MHz ticks -> us
-    # predict (src/ekf.jl:8-43: it runs nine times as often as the update in sim!) and add_features (:84-122) are timed
-    # SEPARATELY, after the timed region: device time of their kernels by HIP events
-    Qp = np.array([[0.5 ** 2, 0.0], [0.0, (3 * math.pi / 180) ** 2]])
-    st.timing(True, kernels=["predict"])
-    st.timing_reset()
-    for _ in range(20):
-        st.predict(8.0, 0.05, 4.0, Qp, 0.025)
-    st.sync()
-    pr_ms, pr_n = st.timing_read()["predict"]
-    st.timing(False)
-    other = {"predict_us": 1e3 * pr_ms / max(pr_n, 1), "predict_calls": pr_n}
-    # the copy floor: the bare read + rewrite of the covariance tiles the down-date touches, on THIS
-    # box, in THIS run, on the SAME buffer -- the boxes of the pool differ by +-6 %, kernel time / floor does not
-    try:
-        floor_ms, floor_form = st.copy_floor(10)
-    except Exception as e:  # noqa: BLE001 -- a diagnostic, never fatal
-        floor_ms, floor_form = None, f"{type(e).__name__}: {e}"
-    gate_info = st.gate_info()             # which form of the gating the steps used (SLAM_GATE_AUTO: the grid from 16384 landmarks on)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, st, last_assoc[0])
+    if args.full:
+        tim = st.timing_read()
+        syrk_min_ms = st.timing_min("syrk")
+        # diagnostics (outside the timed region): every kernel bracketed, and the factorisation kernel's phase stamps
+        ndiag = min(5, total_steps)
+        st.timing(True)
+        st.timing_reset()
+        for i in range(ndiag):
+            step(zs[total_steps - 1 - i])
+        st.sync()
+        tim_all = st.timing_read()
+        st.timing(False)
+        # the timed region brackets every 4th of its steps (5 launches at the driver's 20 steps: a mean whose +-2 % is
+        # the size of a round's gain).  NROOF more steps of the same kind with the down-date bracketed on every one: roofline.frac is
+        # formed from THIS mean; the timed region's stays beside it as avg_launch_ms.
+        st.timing(True, kernels=["syrk"])
+        st.timing_reset()
+        rng_rf = np.random.default_rng(SEED + 104729 + rank)
+        matched_roof = 0
+        for i in range(NROOF):
+            matched_roof += step(zs[(args.warmup + i) % total_steps] + rng_rf.normal(0, 1, zs[0].shape) * np.array([[0.02], [0.2 * math.pi / 180]]))
+        st.sync()
+        roof_n, roof_mean_ms, roof_sd_ms, roof_min_ms = st.timing_stats("syrk")
+        st.timing(False)
+        st.debug_stamps(True)
+        step(zs[-1])
+        st.sync()
+        stamps = st.debug_stamps(False)
+        phases = [(b - a) / 100.0 for a, b in zip(stamps[:6], stamps[1:7])]     # 100 MHz ticks -> us
+        # predict (src/ekf.jl:8-43: it runs nine times as often as the update in sim!) and add_features (:84-122) are timed
+        # SEPARATELY, after the timed region: device time of their kernels by HIP events
+        Qp = np.array([[0.5 ** 2, 0.0], [0.0, (3 * math.pi / 180) ** 2]])
+        st.timing(True, kernels=["predict"])
+        st.timing_reset()
+        for _ in range(20):
+            st.predict(8.0, 0.05, 4.0, Qp, 0.025)
+        st.sync()
+        pr_ms, pr_n = st.timing_read()["predict"]
+        st.timing(False)
+        other = {"predict_us": 1e3 * pr_ms / max(pr_n, 1), "predict_calls": pr_n}
+        # the copy floor: the bare read + rewrite of the covariance tiles the down-date touches, on THIS
+        # box, in THIS run, on the SAME buffer -- the boxes of the pool differ by +-6 %, kernel time / floor does not
+        try:
+            floor_ms, floor_form = st.copy_floor(10)
+        except Exception as e:  # noqa: BLE001 -- a diagnostic, never fatal
+            floor_ms, floor_form = None, f"{type(e).__name__}: {e}"
+        gate_info = st.gate_info()             # which form of the gating the steps used (SLAM_GATE_AUTO: the grid from 16384 landmarks on)
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=RED_DEVICE)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -955,7 +1008,7 @@ def main():
         matched_all = float(matched)
 
     st.close()
-    if not big and rank == 0:
+    if args.full and not big and rank == 0:
         # add_features needs head-room in the pre-allocated capacity: a second handle with 64 spare landmarks, same state
         st2 = pkg.EKFSlamState(x, P, dtype=args.dtype, max_landmarks=N + 64, device=local_rank)
         rng_af = np.random.default_rng(SEED + 31)
@@ -971,6 +1024,22 @@ def main():
 
     out = None
     if rank == 0:
+        out = {
+            "metric": "EKF updates/sec @ 10k landmarks" if N == 10000 else f"EKF updates/sec @ {N} landmarks",
+            "value": matched_all / elapsed,
+            "unit": "obs-updates/s (one observation assimilated = one update)",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": elapsed / args.steps * 1e3,
+            "steps_per_s": world * args.steps / elapsed, "prewarm_steps": prewarm_steps,
+            "matched_per_step": matched / args.steps,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": args.dtype, "data": "synthetic",
+            "config": {"workload": f"EKF-SLAM observation step (associate+update; no new features arise), N={N} landmarks (n={n}), nz={nz} obs/step, "
+                                   f"gates {GATE1}/{GATE2}, {args.form} form, state resident in HBM",
+                       "landmarks": N, "obs_per_step": nz, "form": args.form,
+                       "parallelism": "single GPU" if world == 1 else f"{world} independent replicas (EKF does not shard)"},
+        }
+    if rank == 0 and args.full:
         esz = 4 if args.dtype == "f32" else 8
         syrk_ms, syrk_n = tim["syrk"]
         syrk_avg_s = (syrk_ms / max(syrk_n, 1)) * 1e-3
@@ -1049,27 +1118,14 @@ def main():
                                    f"the down-date's band-major order, no panels, no matrix cores), 10 individually timed passes of each launch form on "
                                    f"this run's own matrix, the FASTEST pass ({floor_form}); kernel_over_floor = average launch / floor, "
                                    f"kernel_over_floor_min = fastest bracketed launch / floor (the box-independent figure)")
-        out = {
-            "metric": "EKF updates/sec @ 10k landmarks" if N == 10000 else f"EKF updates/sec @ {N} landmarks",
-            "value": matched_all / elapsed,
-            "unit": "obs-updates/s (one observation assimilated = one update)",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3,
-            "steps_per_s": world * args.steps / elapsed, "prewarm_steps": prewarm_steps,
-            "matched_per_step": matched / args.steps,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": args.dtype, "data": "synthetic",
-            "config": {"workload": f"EKF-SLAM observation step (associate+update; no new features arise), N={N} landmarks (n={n}), nz={nz} obs/step, "
-                                   f"gates {GATE1}/{GATE2}, {args.form} form, state resident in HBM",
-                       "landmarks": N, "obs_per_step": nz, "form": args.form,
-                       "parallelism": "single GPU" if world == 1 else f"{world} independent replicas (EKF does not shard)"},
+        out.update({
             "roofline": roof,
             "kernel_ms_per_step": {k: v[0] / max(ndiag, 1) for k, v in tim_all.items()},
             "traffic_note": traffic_note,
             "kernel_ms_per_step_note": f"{ndiag} extra steps after the timed region with every kernel bracketed by events",
             "other_kernels": other,
             "factor_phases_us": dict(zip(["innovation", "build_S", "symmetrise", "eliminate", "y_g", "emit_C"], phases)),
-        }
+        })
         # the gating sweep (K1): 12 state values per landmark read once per sweep, nz * N pairs evaluated
         g_ms = tim_all["gate"][0] / max(ndiag, 1)
         if g_ms > 0:
@@ -1092,7 +1148,7 @@ def main():
         out["configs"] = configs_guarded(pkg, max(args.steps, 20), args.warmup, local_rank, pmc_cfg)
     # the FastSLAM leg comes AFTER the headline's numbers are complete, under a deadline: whatever happens to it on a node
     # this code has never seen (ranks on several physical GPUs, IPC mappings, a peer that dies), the line still comes out
-    fast = None if args.no_fastslam else fastslam_guarded(out, rank, world, pkg, world, rank, local_rank, max(args.steps, 10),
+    fast = None if args.no_fastslam or not args.full else fastslam_guarded(out, rank, world, pkg, world, rank, local_rank, max(args.steps, 10),
                                                           args.warmup, fence)
     if rank == 0:
         if fast is not None:

@@ -285,6 +285,47 @@ def test_consecutive_fp32_observation_steps_on_the_bench_workload(pkg):
         del P, Po, Pg
 
 
+def test_bench_plain_run_and_its_dumped_outputs(pkg, tmp_path):
+    """`bench.py` without --full prints the headline alone, its K timed steps as asked; --dump-outputs writes what the last
+    timed step left: float arrays below 64 MB, identical in two runs with the same arguments (the device warm-up runs for
+    a fixed TIME, i.e. a varying number of steps: it must not reach the timed steps' inputs), and equal bit for bit to the
+    W + K steps driven here through the library from the workload's state."""
+    import json
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    if root not in sys.path:
+        sys.path.insert(0, root)
+    import bench as B
+    N, nz, W, K = 1000, 16, 3, 7
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f"run{run}"
+        r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", str(K), "--warmup", str(W), "--landmarks", str(N),
+                            "--obs", str(nz), "--dump-outputs", str(d)], cwd=root, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(line), line
+        assert line["steps"] == K and line["ms_per_step"] > 0 and line["dtype"] == "f32", line
+        assert not {"roofline", "kernel_ms_per_step", "cpu_baseline", "configs", "fastslam"} & set(line), sorted(line)
+        files = sorted(d.glob("*.npy"))
+        assert sum(f.stat().st_size for f in files) <= 64 << 20
+        dumps.append({f.stem: np.load(f) for f in files})
+    assert {"assoc", "x", "P_diag"} <= set(dumps[0]) and set(dumps[0]) == set(dumps[1])
+    for name, a in dumps[0].items():
+        assert a.dtype in (np.float32, np.float64), name
+        assert np.array_equal(a, dumps[1][name]), name
+    x, P, zs = B.make_workload(N, nz, W + K, B.SEED)
+    st = pkg.EKFSlamState(x, P, dtype="f32", max_landmarks=N)
+    for z in zs:
+        a = st.observe(z, B.R, B.GATE1, B.GATE2)
+    got = dumps[0]
+    assert np.array_equal(got["assoc"], a.astype(np.float64))
+    assert np.array_equal(got["x"], st.download("x")) and np.array_equal(got["P_diag"], st.diag())
+    cols = got["P_column_ids"].astype(int)
+    assert np.array_equal(got["P_columns"], np.stack([st.get_block(0, c, st.n, 1)[:, 0] for c in cols], axis=1))
+    st.close()
+
+
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("N", [0, 1, 2, 35, 100])
 def test_single_calls_against_golden(pkg, single, dtype, N):

@@ -1140,7 +1140,7 @@ def test_bench_fastslam_leg_with_two_ranks_on_one_card():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, SLAM_BENCH_REHEARSE="1", SLAM_BENCH_NP="65536", HSA_ENABLE_IPC_MODE_LEGACY="0", SLAM_BENCH_PF_BUDGET_S="400")
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--no-pmc",
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--gpus", "2", "--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--no-pmc",
                         "--no-configs", "--landmarks", "1000", "--obs", "16", "--prewarm-ms", "10"], cwd=root, env=env,
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]

@@ -1,11 +1,13 @@
-# PMC passes over the bench (one counter group per run; no trace domains besides kernel-trace).
-mkdir -p gpurun_out/pmc
+# PMC passes over the bench (one counter group per run; no trace domains besides kernel-trace).  Run from the repository
+# root; output under $SLAM_PROFILE_OUT (default profile_out/)/pmc.
+ROOT=$(pwd)
+OUT=$(realpath -m ${SLAM_PROFILE_OUT:-profile_out})/pmc
+mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-OUT=$GRAFT_REPO_ROOT/gpurun_out/pmc
 rocprofv3 -L > $OUT/counters_list.txt 2>&1
 run() {  # name, counters...
   name=$1; shift
-  timeout -k 10 300 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $OUT/$name -o p -- python3 $GRAFT_REPO_ROOT/bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-pmc --no-configs > $OUT/$name.log 2>&1
+  timeout -k 10 300 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $OUT/$name -o p -- python3 $ROOT/bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-pmc --no-configs > $OUT/$name.log 2>&1
   echo "$name exit $?" >> $OUT/summary.log
 }
 run sq1 SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU
