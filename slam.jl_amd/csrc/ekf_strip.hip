@@ -65,12 +65,14 @@ __global__ __launch_bounds__(256) void augment_kernel(T* __restrict__ x, T* __re
                     GP[r][cc] = Ga[r][0] * Pvv[0][cc] + Ga[r][1] * Pvv[1][cc] + Ga[r][2] * Pvv[2][cc];
             for (int r = 0; r < 2; ++r)
                 for (int cc = 0; cc < 2; ++cc) GR[r][cc] = Gz[r][0] * R[0][cc] + Gz[r][1] * R[1][cc];
+            // the lower triangle of the block, each entry formed ONCE and stored with its mirror: formed separately, (0, 1) and
+            // (1, 0) round differently in fp64 and P would not be bit-for-bit symmetric
             for (int r = 0; r < 2; ++r)
-                for (int cc = 0; cc < 2; ++cc) {
+                for (int cc = 0; cc <= r; ++cc) {
                     const double val = (GP[r][0] * Ga[cc][0] + GP[r][1] * Ga[cc][1] + GP[r][2] * Ga[cc][2]) +
                                        (GR[r][0] * Gz[cc][0] + GR[r][1] * Gz[cc][1]);
-                    p_store(P, ld, tlog, fa + r, fa + cc, (T)val);      // (the entry above the diagonal exists inside a diagonal tile only)
-                    if (r >= cc) side_note(side, side_n, fa + r, fa + cc, (T)val);
+                    p_store_sym(P, ld, tlog, fa + r, fa + cc, (T)val);  // (the entry above the diagonal exists inside a diagonal tile only)
+                    side_note(side, side_n, fa + r, fa + cc, (T)val);
                     // the new landmark's variances enter the pre-gate's bound (ekf_gate.hip): bit pattern of a
                     // non-negative double orders like the integer; anything else disables the pre-gate (+inf)
                     if (r == cc) {
@@ -309,10 +311,13 @@ __global__ __launch_bounds__(256) void predict_kernel(T* __restrict__ x, T* __re
             GP[r][cc] = Gv[r][0] * Pvv[0][cc] + Gv[r][1] * Pvv[1][cc] + Gv[r][2] * Pvv[2][cc];
     for (int r = 0; r < 3; ++r)
         for (int cc = 0; cc < 2; ++cc) GQ[r][cc] = Gu[r][0] * Q[0][cc] + Gu[r][1] * Q[1][cc];
+    // the lower triangle, each entry formed once and mirrored: (r, cc) and (cc, r) formed separately round differently
     for (int r = 0; r < 3; ++r)
-        for (int cc = 0; cc < 3; ++cc)
+        for (int cc = 0; cc <= r; ++cc) {
             out[r][cc] = (GP[r][0] * Gv[cc][0] + GP[r][1] * Gv[cc][1] + GP[r][2] * Gv[cc][2]) +
                          (GQ[r][0] * Gu[cc][0] + GQ[r][1] * Gu[cc][1]);
+            out[cc][r] = out[r][cc];
+        }
     for (int r = 0; r < 3; ++r)
         for (int cc = 0; cc < 3; ++cc) P[p_off(ld, tlog, r, cc)] = (T)out[r][cc];
     const double x0 = (double)x[0], x1 = (double)x[1];
