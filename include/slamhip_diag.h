@@ -1,6 +1,7 @@
 /* slamhip_diag.h -- the MEASUREMENT and introspection entry points of libslamhip.so: event timing of the kernels, phase
  * stamps, the copy floor of the down-date, which form of the gating ran, what the exchange between the ranks of a sharded
- * filter saw.  Nothing here is part of the drop-in boundary (include/slamhip.h: what the reference's module surface maps
+ * filter saw, and the read-outs of the particle filter's state (its map, one particle) that the reference has no counterpart
+ * for.  Nothing here is part of the drop-in boundary (include/slamhip.h: what the reference's module surface maps
  * onto); bench.py, the tests and the profiling tools use them.  Same conventions: extern "C", int status codes. */
 #ifndef SLAMHIP_DIAG_H
 #define SLAMHIP_DIAG_H
@@ -70,6 +71,34 @@ int slam_pf_comm_info(slam_pf_t h, int64_t out[4]);
  * statistics folded, decision taken, bookkeeping done, published; [6] the collecting workgroup finished its own share,
  * [7] = [0] + 100 x the number of polls it needed.  Waits for the queue. */
 int slam_pf_debug_stamps(slam_pf_t h, uint64_t out[8]);
+
+/* ---- state read-outs ------------------------------------------------------------------------------------------------------
+ * The FastSLAM map without downloading the particles: one pass over the landmark records WHERE THEY ARE (through the lazy
+ * resampling's ancestor tables).  All three calls leave the auto mode as slam_pf_download does, honour a pending
+ * normalisation shift and synchronise.  A filter that lives wholly on this shard is not changed in any way (no record moves,
+ * its log-weights stay as stored); on a filter with peers attached the calls are COLLECTIVE: the remote records come home
+ * first, as for slam_pf_download.  Results are the same bit for bit from call to call (fixed-order fp64 sums, no atomics).
+ *
+ * A particle contributes to landmark l only where its record is in use: Pxx > 0 (neither the Pxx = -1 mark of
+ * slam_pf_clear_landmarks nor the all-zero record of a landmark never seen).  One exception: slam_pf_init_landmarks with
+ * var = 0 writes used records with Pxx == 0; a record with Pxx == 0 counts when its landmark has been initialised or
+ * observed by a known-correspondence call (the library's `seen` state), which no empty slot and no unseen landmark is.  w = exp(log-weight - pending shift), the weights
+ * slam_pf_get_weights returns. */
+
+/* The LOCAL sums, out[(1 + cnt) * 10] doubles; ids 1-based as in slam_pf_update_known, NULL = 1..nl (cnt ignored):
+ *   row 0 (pose):      W, sum w x, sum w y, sum w x^2, sum w x y, sum w y^2, sum w sin(phi), sum w cos(phi), 0, n_local
+ *   row 1 + i (ids[i]): W_l, sum w mx, sum w my, sum w mx^2, sum w mx my, sum w my^2, sum w Pxx, sum w Pxy, sum w Pyy, count_l
+ * (W_l, count_l: weight mass and number of the contributing particles).  A sharded filter adds them over its ranks. */
+int slam_pf_map_sums(slam_pf_t h, const int32_t* ids, int cnt, double* out);
+
+/* The whole filter on this shard: out[cnt * 8] = {mass W_l / W, mean x, mean y, Cxx, Cxy, Cyy, count_l, 0} per landmark with
+ * C = sum w P / W_l + (sum w m m' / W_l - mean mean'): the moment-matched Gaussian of the particles' mixture.  Mass 0: the
+ * rest 0. */
+int slam_pf_get_map(slam_pf_t h, const int32_t* ids, int cnt, double* out);
+
+/* Local particle `idx` (-1: the one with the largest log-weight, the lowest index on a tie): its global id, log-weight, pose
+ * and, if lm != NULL, its nl x 5 landmark records {x, y, Pxx, Pxy, Pyy} (row-major, double).  gid, logw, pose may be NULL. */
+int slam_pf_get_particle(slam_pf_t h, int64_t idx, int64_t* gid, double* logw, double pose[3], double* lm);
 
 #ifdef __cplusplus
 }

@@ -16,7 +16,7 @@ export SlamState, EKFSlamState, set_state!, predict, update, add_features, assoc
        compute_association, predict_observation, mpi_to_pi,
        ekf_predict!, ekf_update!, augment!, observe!, cov_block, cov_diag, landmark_blocks, gate_mode!, gate_info, state_written!, feature_ellipses, vehicle_ellipse,
        PFSlamState, set_pose!, init_landmarks!, pf_predict!, update_known!, step!, step_async!, step_async_batch!, flush!,
-       resample!, mean_pose, weights, particles, peer_blob, attach_peers!, peer_selftest, detach_peers!, comm_info
+       resample!, mean_pose, weights, particles, pf_map, pf_best_particle, peer_blob, attach_peers!, peer_selftest, detach_peers!, comm_info
 
 const libslamhip = get(ENV, "SLAMHIP_LIB", joinpath(@__DIR__, "libslamhip.so"))
 
@@ -473,6 +473,30 @@ function weights(s::PFSlamState)
     out = zeros(Float64, s.n)
     check(ccall((:slam_pf_get_weights, libslamhip), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), s.handle, out))
     out
+end
+
+"""
+The map of the filter (whole filter on this shard) without downloading the particles: 8 x cnt matrix, per landmark
+[mass, mean x, mean y, Cxx, Cxy, Cyy, count, 0] -- the moment-matched Gaussian of the particles' mixture
+(slam_pf_get_map).  `ids`: 1-based landmark ids, `nothing` = all.
+"""
+function pf_map(s::PFSlamState, ids::Union{Nothing,AbstractVector} = nothing)
+    cnt = ids === nothing ? s.max_landmarks : length(ids)
+    out = zeros(Float64, 8, cnt)
+    idv = ids === nothing ? Ptr{Int32}(C_NULL) : Vector{Int32}(ids)
+    check(ccall((:slam_pf_get_map, libslamhip), Cint, (Ptr{Cvoid}, Ptr{Int32}, Cint, Ptr{Cdouble}), s.handle, idv, cnt, out))
+    out
+end
+
+"The local particle with the largest log-weight: (global id, log-weight, pose [x, y, phi], records 5 x max_landmarks)."
+function pf_best_particle(s::PFSlamState)
+    gid = Ref{Int64}(0)
+    logw = Ref{Cdouble}(0.0)
+    pose = zeros(Float64, 3)
+    lm = zeros(Float64, 5, s.max_landmarks)
+    check(ccall((:slam_pf_get_particle, libslamhip), Cint, (Ptr{Cvoid}, Int64, Ref{Int64}, Ref{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                s.handle, -1, gid, logw, pose, lm))
+    gid[], logw[], pose, lm
 end
 
 "Download: (pose 3 x n ... as n x 3, logw n, lm n x 5 x max_landmarks): the device's SoA arrays, particle index fastest."

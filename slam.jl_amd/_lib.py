@@ -68,7 +68,7 @@ _h = C.c_void_p
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
 
-#: every symbol include/slamhip.h declares: name -> (restype, argtypes)
+#: every symbol include/slamhip.h and include/slamhip_diag.h declare: name -> (restype, argtypes)
 SIGNATURES = {
     "slam_last_error": (C.c_char_p, []),
     "slam_device_count": (C.c_int, []),
@@ -149,6 +149,9 @@ SIGNATURES = {
     "slam_pf_resample": (C.c_int, [_h, C.c_double, C.POINTER(C.c_int)]),
     "slam_pf_get_mean_pose": (C.c_int, [_h, _dp]),
     "slam_pf_get_weights": (C.c_int, [_h, _dp]),
+    "slam_pf_map_sums": (C.c_int, [_h, _ip, C.c_int, _dp]),
+    "slam_pf_get_map": (C.c_int, [_h, _ip, C.c_int, _dp]),
+    "slam_pf_get_particle": (C.c_int, [_h, C.c_int64, C.POINTER(C.c_int64), _dp, _dp, _dp]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -1,6 +1,6 @@
 // pf_internal.h -- the FastSLAM particle path: state, control blocks and the host-side pieces shared by its translation
 // units (pf_legacy.hip: the rank-local kernels and entry points; pf_auto.hip: the step without the host; pf_peers.hip: the
-// sharding behind the C ABI).  Device code common to the kernels: pf_device.h.
+// sharding behind the C ABI; pf_map.hip: the map and particle read-outs).  Device code common to the kernels: pf_device.h.
 #pragma once
 #include <stdlib.h>
 #include <unistd.h>
@@ -193,6 +193,8 @@ struct slam_pf {
     double halt_gmax;            // largest normalised log-weight of the halted step
     long long last_resampled_seq;
     double* d_pb_lines;          // pf_batch.hip: the workgroups' statistics lines of the persistent launch, two parities (allocated at the first one)
+    void* d_mapws;               // pf_map.hip: grow-only scratch of the read-outs (partials, work list, results; allocated at the first one)
+    size_t mapws_bytes;
 };
 
 // ---- observation codes, per-landmark state words, sizes ------------------------------------------------------------------

@@ -31,7 +31,8 @@ import numpy as np
 from ._lib import SLAM_F32, SLAM_F64, SLAM_PF_HALTED, SLAM_PF_PEER_BLOB_BYTES, check, lib
 from .ekf import _obs, _small, _ptr
 
-__all__ = ["PFShard", "PFSlamState", "FastSLAM", "philox_uniform", "small", "shared_page", "attach_local_peers"]
+__all__ = ["PFShard", "PFSlamState", "FastSLAM", "philox_uniform", "small", "shared_page", "attach_local_peers",
+           "finalise_map", "ellipse_axes", "MapSnapshot"]
 
 _M0, _M1, _W0, _W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
 STREAM_RESAMPLE = 2
@@ -47,6 +48,72 @@ def philox_uniform(step: int, stream: int, seed: int) -> float:
         c = [((p1 >> 32) ^ c[1] ^ k0) & 0xFFFFFFFF, p1 & 0xFFFFFFFF, ((p0 >> 32) ^ c[3] ^ k1) & 0xFFFFFFFF, p0 & 0xFFFFFFFF]
         k0, k1 = (k0 + _W0) & 0xFFFFFFFF, (k1 + _W1) & 0xFFFFFFFF
     return ((c[0] >> 8) + 0.5) / 16777216.0
+
+
+def finalise_map(sums):
+    """The map from the (summed) rows of ``PFShard.map_sums``: ``sums`` [1 + cnt, 10] (row 0 the pose row) ->
+    [cnt, 8] = {mass W_l / W, mean x, mean y, Cxx, Cxy, Cyy, count, 0} per landmark with
+    C = sum w P / W_l + (sum w m m' / W_l - mean mean'), the moment-matched Gaussian of the particles' mixture; a
+    landmark without mass is a row of zeros.  The same arithmetic as ``slam_pf_get_map``, for one rank and for the sum
+    over many."""
+    s = np.asarray(sums, dtype=np.float64).reshape(-1, 10)
+    W, r = s[0, 0], s[1:]
+    out = np.zeros((r.shape[0], 8))
+    ok = (r[:, 0] > 0.0) & (W > 0.0)
+    Wl = r[ok, 0]
+    mx, my = r[ok, 1] / Wl, r[ok, 2] / Wl
+    out[ok, 0] = Wl / W
+    out[ok, 1], out[ok, 2] = mx, my
+    out[ok, 3] = r[ok, 6] / Wl + (r[ok, 3] / Wl - mx * mx)
+    out[ok, 4] = r[ok, 7] / Wl + (r[ok, 4] / Wl - mx * my)
+    out[ok, 5] = r[ok, 8] / Wl + (r[ok, 5] / Wl - my * my)
+    out[ok, 6] = r[ok, 9]
+    return out
+
+
+def ellipse_axes(cxx, cxy, cyy):
+    """(rx, ry, phi) of the covariance ellipses [[cxx, cxy], [cxy, cyy]] (arrays) with the convention ``slam_ekf_ellipses``
+    documents: rx <= ry the square roots of the ascending eigenvalues, phi the direction of the FIRST (smaller
+    eigenvalue's) eigenvector in [-pi/2, pi/2]."""
+    cxx, cxy, cyy = (np.asarray(v, dtype=np.float64) for v in (cxx, cxy, cyy))
+    half, mean = 0.5 * (cxx - cyy), 0.5 * (cxx + cyy)
+    rad = np.hypot(half, cxy)
+    l1, l2 = np.maximum(mean - rad, 0.0), np.maximum(mean + rad, 0.0)
+    # eigenvector of the smaller eigenvalue l1: (cxy, l1 - cxx) or, where that one vanishes, (l1 - cyy, cxy)
+    vx = np.where(np.abs(l1 - cxx) >= np.abs(l1 - cyy), cxy, l1 - cyy)
+    vy = np.where(np.abs(l1 - cxx) >= np.abs(l1 - cyy), l1 - cxx, cxy)
+    iso = (vx == 0.0) & (vy == 0.0)                         # a circle (or a diagonal matrix with cxx <= cyy): the x axis
+    vx = np.where(iso, 1.0, vx)
+    flip = (vx < 0.0) | ((vx == 0.0) & (vy < 0.0))
+    phi = np.arctan2(np.where(flip, -vy, vy), np.where(flip, -vx, vx))
+    return np.sqrt(l1), np.sqrt(l2), phi
+
+
+class MapSnapshot:
+    """The read-outs of a particle filter from one set of map sums ([1 + nl, 10], ``FastSLAM.map_sums``): host arithmetic only."""
+
+    def __init__(self, sums):
+        self.sums = np.asarray(sums, dtype=np.float64).reshape(-1, 10)
+        self.map = finalise_map(self.sums)
+
+    def pose(self):
+        s = self.sums[0]
+        return np.array([s[1] / s[0], s[2] / s[0], math.atan2(s[6], s[7])])
+
+    @property
+    def N(self):
+        return int(np.count_nonzero(self.map[:, 0] > 0.0))
+
+    def feature_ellipses(self):
+        m = self.map[self.map[:, 0] > 0.0]
+        rx, ry, phi = ellipse_axes(m[:, 3], m[:, 4], m[:, 5])
+        return np.vstack([m[:, 1], m[:, 2], rx, ry, phi])
+
+    def vehicle_ellipse(self):
+        s = self.sums[0]
+        mx, my = s[1] / s[0], s[2] / s[0]
+        rx, ry, phi = ellipse_axes(s[3] / s[0] - mx * mx, s[4] / s[0] - mx * my, s[5] / s[0] - my * my)
+        return np.array([mx, my, math.atan2(s[6], s[7]), float(rx), float(ry), float(phi)])
 
 
 class _Small:
@@ -340,6 +407,44 @@ class PFShard:
         out = np.empty(self.n)
         check(lib.slam_pf_get_weights(self._h, _ptr(out)))
         return out
+
+    # -- the map without downloading the particles (slam_pf_map_sums / slam_pf_get_map / slam_pf_get_particle) ---
+    @staticmethod
+    def _ids(ids):
+        if ids is None:
+            return None, None, 0
+        idv = np.ascontiguousarray(np.asarray(ids, dtype=np.int32).reshape(-1))
+        cnt = idv.shape[0]
+        if cnt == 0:
+            idv = np.zeros(1, dtype=np.int32)        # (a NULL pointer would mean "all landmarks")
+        return idv, _ptr(idv, C.c_int32), cnt
+
+    def map_sums(self, ids=None):
+        """This shard's sums of the weighted map, [1 + cnt, 10] float64: row 0 the pose row {W, sum w x, w y, w x^2,
+        w x y, w y^2, w sin(phi), w cos(phi), 0, n_local}, row 1 + i landmark ``ids[i]`` (1-based; None: all)
+        {W_l, sum w mx, w my, w mx^2, w mx my, w my^2, w Pxx, w Pxy, w Pyy, count_l}.  One pass over the records where
+        they are; a filter wholly on this shard is not changed (collective with peers attached)."""
+        _idv, ptr, cnt = self._ids(ids)
+        out = np.empty((1 + (self.nl if ids is None else cnt), 10))
+        check(lib.slam_pf_map_sums(self._h, ptr, cnt, _ptr(out)))
+        return out
+
+    def get_map(self, ids=None):
+        """slam_pf_get_map (whole filter on this shard): [cnt, 8] = {mass, mean x, mean y, Cxx, Cxy, Cyy, count, 0}."""
+        _idv, ptr, cnt = self._ids(ids)
+        out = np.empty((self.nl if ids is None else cnt, 8))
+        check(lib.slam_pf_get_map(self._h, ptr, cnt, _ptr(out)))
+        return out
+
+    def particle(self, idx=-1, landmarks=True):
+        """Local particle ``idx`` (-1: the one with the largest log-weight, lowest index on a tie):
+        (global id, log-weight, pose [3], records [nl, 5] or None), float64."""
+        gid, lw = C.c_int64(), C.c_double()
+        pose = np.empty(3)
+        lm = np.empty((self.nl, 5)) if landmarks else None
+        check(lib.slam_pf_get_particle(self._h, int(idx), C.byref(gid), C.byref(lw), _ptr(pose),
+                                       _ptr(lm) if landmarks else None))
+        return int(gid.value), float(lw.value), pose, lm
 
     # -- resampling pieces (torch tensors on this shard's device) ---------------------------------
     def logw_tensor(self):
@@ -719,6 +824,29 @@ class FastSLAM:
         s = self.comm.allreduce_sum(list(self.shard.mean_pose_sums()))
         return np.array([s[0], s[1], math.atan2(s[2], s[3])])       # weights are normalised: sums are means
 
+    # -- the map ---------------------------------------------------------------------------------------------------------
+    def map_sums(self, ids=None):
+        """The filter's sums of the weighted map (PFShard.map_sums added over the ranks), [1 + cnt, 10]."""
+        local = self.shard.map_sums(ids)
+        return np.asarray(self.comm.allreduce_sum(local.reshape(-1).tolist()), dtype=np.float64).reshape(local.shape)
+
+    def map(self, ids=None):
+        """The map: [cnt, 8] = {mass, mean x, mean y, Cxx, Cxy, Cyy, count, 0} per landmark (``ids`` 1-based, None: all),
+        the moment-matched Gaussian of the particles' mixture (see finalise_map).  Collective for a sharded filter."""
+        return finalise_map(self.map_sums(ids))
+
+    def best_particle(self):
+        """The particle with the largest log-weight of the whole filter (lowest global id on a tie):
+        (global id, log-weight, pose [3], records [nl, 5]), the same on every rank.  Collective for a sharded filter."""
+        gid, lw, pose, lm = self.shard.particle(-1)
+        if self.comm.world == 1:
+            return gid, lw, pose, lm
+        table = self.comm.all_gather_scalars([lw, float(gid)])
+        best = max(range(len(table)), key=lambda r: (table[r][0], -table[r][1]))
+        rec = np.concatenate([pose, lm.reshape(-1)]) if best == self.comm.rank else np.zeros(3 + lm.size)
+        rec = np.asarray(self.comm.allreduce_sum(rec.tolist()), dtype=np.float64)       # (the owner's record + zeros)
+        return int(table[best][1]), float(table[best][0]), rec[:3], rec[3:].reshape(lm.shape)
+
 
 def socket_host():
     import socket
@@ -825,6 +953,32 @@ class PFSlamState(FastSLAM):
             self.selftest_ok = None
         super().__init__(shard, comm, neff_frac)
         self.n = n
+
+    # -- the read-outs telemetry.monitor_messages asks a state for (as EKFSlamState has them) ---------------------------
+    def snapshot(self):
+        """The map and the pose of this moment from ONE query (one pass over the records, one all-reduce on a sharded
+        filter): a :class:`MapSnapshot` with ``pose()``, ``N``, ``feature_ellipses()``, ``vehicle_ellipse()`` -- what
+        ``telemetry.monitor_messages`` asks a state for.  The methods below are each a query of their own (``pose`` and
+        ``vehicle_ellipse`` of the pose row alone); a caller that wants all of them takes a snapshot."""
+        return MapSnapshot(self.map_sums())
+
+    def pose(self):
+        """The weighted mean pose [x, y, phi]."""
+        return MapSnapshot(self.map_sums([])).pose()
+
+    @property
+    def N(self):
+        """Landmarks the filter has a map of (weight mass > 0)."""
+        return self.snapshot().N
+
+    def feature_ellipses(self):
+        """5 x N: cx, cy, rx, ry, phi of the landmarks with mass (in landmark order), the convention of
+        ``EKFSlamState.feature_ellipses`` (rx <= ry, phi of the first eigenvector in [-pi/2, pi/2])."""
+        return self.snapshot().feature_ellipses()
+
+    def vehicle_ellipse(self):
+        """[cx, cy, vehicle_phi, rx, ry, phi] of the particles' pose cloud."""
+        return MapSnapshot(self.map_sums([])).vehicle_ellipse()
 
     def close(self):
         """Collective for a sharded filter with peers: remote records are brought home, the peers are detached, then a
