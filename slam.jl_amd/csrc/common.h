@@ -151,8 +151,11 @@ struct slam_ekf {
     int grid_n_seen;     // N when the fold / rebuild check was last enqueued
 
     // gating partials
-    double* gate_part;   // [gate_blocks][ocap][3]
-    int gate_blocks_cap;
+    double* gate_part;   // the sweep's candidate lists (gate_kernel, ekf_gate.hip), per chunk of 128 observations:
+                         // [128][gate_blocks_cap] entries {nd, landmark as a double}, then int32 cnt[128], int32 near[128]
+    int gate_blocks_cap; // entries per observation.  A workgroup appends AT MOST ONE entry per observation (one of its waves
+                         // owns the observation and lane 0 appends the wave's best), so a capacity >= the number of
+                         // workgroups, ceil(N / 64), can never overflow (launch_gate refuses a smaller one)
 
     // small device scratch + pinned mirror for scalar outputs
     double* d_small;     // 64 doubles: [0..11] small results, [40..55] debug stamps, [56] the ready word factor_w1_kernel's workgroups meet on

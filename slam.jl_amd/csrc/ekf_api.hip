@@ -139,7 +139,9 @@ int ensure_obs_capacity(slam_ekf* h, int nobs) {
     if ((rc = dev_alloc_zero(&h->idfbuf, sizeof(int32_t) * cap, h->stream))) return rc;
     if ((rc = dev_alloc_zero(&h->d_assoc, sizeof(int32_t) * cap, h->stream))) return rc;
     if ((rc = dev_alloc_zero(&h->znbuf, sizeof(double) * 2 * cap, h->stream))) return rc;
-    // gating partials: [blocks][<=256 observations per sweep][3]
+    // the sweep's candidate lists: per chunk of 128 observations [128][gate_blocks_cap] entries of 2 doubles {nd, landmark},
+    // then two int32 words per observation (cnt, near): 256 * cap + 128 doubles, inside the 768 * cap allocated here.
+    // At most one entry per workgroup per observation, and cap >= ceil(maxN / 64) workgroups: a list cannot overflow.
     h->gate_blocks_cap = (h->maxN + 63) / 64 + 1;
     if ((rc = dev_alloc_zero(&h->gate_part, sizeof(double) * 3 * 256 * (size_t)h->gate_blocks_cap, h->stream))) return rc;
     HIP_TRY(hipHostMalloc((void**)&h->h_obs, sizeof(double) * 2 * cap, hipHostMallocDefault));
