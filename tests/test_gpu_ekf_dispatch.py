@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from oracle import ekf_ref as O
+from tests import strip_ref as S
 from tests.test_gpu_ekf import R, TOL, check_side, noisy_obs, random_state, relerr, relerr_cov, rounded
 
 pytestmark = pytest.mark.gpu
@@ -285,10 +286,26 @@ def test_one_handle_through_a_schedule(pkg, monkeypatch, dtype):
                 xn, Pn = O.add_features_sparse(xo, Po, zn, R)
                 assert st.N == N + m
                 _check(st, xn, Pn, Po, dtype, what)
+                # ... and entry by entry, to the rounding-level bound of tests/strip_ref.py
+                n0 = len(xo)
+                xg, Pg = st.download()
+                ref = S.add_features_ref(xo[:3], Po[:, 0:3], zn, R)
+                S.assert_within(Pg[n0:, :n0], ref["cross"], dtype, S.C_STRIP, "add_features cross: " + what)
+                S.assert_within(Pg[n0:, n0:], ref["new"], dtype, S.C_BLOCK, "add_features new: " + what)
+                S.assert_within(xg[n0:], ref["x"], dtype, S.C_STRIP, "add_features x: " + what)
+                assert np.array_equal(xg[:n0], xo) and np.array_equal(Pg[:n0, :n0], Po), what
             else:
                 xo, Po = rounded(st)
                 st.predict(8.0, 0.05, 4.0, Q, 0.025)
                 xn, Pn = O.predict_sparse(xo.copy(), Po.copy(), 8.0, 0.05, 4.0, Q, 0.025)
                 _check(st, xn, Pn, Po, dtype, what)
+                xg, Pg = st.download()
+                ref = S.predict_ref(xo[:3], Po[:, 0:3], 8.0, 0.05, 4.0, Q, 0.025)
+                S.assert_within(Pg[3:, 0:3], ref["strip"], dtype, S.C_STRIP, "predict strip: " + what)
+                S.assert_within(Pg[0:3, 0:3], ref["vv"], dtype, S.C_BLOCK, "predict P_vv: " + what)
+                S.assert_within(xg[0:3], ref["x"], dtype, S.C_STRIP, "predict x: " + what)
+                assert np.array_equal(xg[3:], xo[3:]) and np.array_equal(Pg[3:, 3:], Po[3:, 3:]), what
+        # what the schedule leaves behind: zero padding, bit-symmetric diagonal tiles, readers and side array in step
+        S.check_storage(st, Pg=st.download("cov"), what=f"{dtype} after the schedule")
     finally:
         st.close()
