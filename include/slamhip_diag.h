@@ -1,7 +1,7 @@
 /* slamhip_diag.h -- the MEASUREMENT and introspection entry points of libslamhip.so: event timing of the kernels, phase
  * stamps, the copy floor of the down-date, which form of the gating ran, what the exchange between the ranks of a sharded
- * filter saw, and the read-outs of the particle filter's state (its map, one particle) that the reference has no counterpart
- * for.  Nothing here is part of the drop-in boundary (include/slamhip.h: what the reference's module surface maps
+ * filter saw, the read-outs of the particle filter's state (its map, one particle) and the EKF's map management (landmark removal) that
+ * the reference has no counterpart for.  Nothing here is part of the drop-in boundary (include/slamhip.h: what the reference's module surface maps
  * onto); bench.py, the tests and the profiling tools use them.  Same conventions: extern "C", int status codes. */
 #ifndef SLAMHIP_DIAG_H
 #define SLAMHIP_DIAG_H
@@ -56,6 +56,18 @@ int slam_ekf_debug_stamps(slam_ekf_t h, int enable, uint64_t* out16);
  * down-date's launch time over this figure compares across the boxes of a pool whose memory systems differ by a few
  * per cent.  Synchronises; the state is unchanged. */
 int slam_ekf_copy_floor(slam_ekf_t h, int reps, double out[2]);
+
+/* ---- map management: no counterpart in the reference ----------------------------------------------------------------------
+ * The reference's map only grows (every observation outside gate2 becomes a landmark, src/data-association.jl).  For a
+ * Gaussian, marginalising a landmark out is deleting its two rows / columns of P and its two entries of x: no arithmetic. */
+
+/* Remove landmarks ids[0..cnt) (1-based, as idf; any order) from the map: x <- x[keep], P <- P[keep, keep], bit for bit;
+ * the remaining landmarks keep their order and are renumbered 1..N-cnt.  new_index (may be NULL; N_old entries):
+ * new_index[j-1] = the new id of old landmark j, 0 if it was removed.  cnt == 0: nothing happens.
+ * In place on the device through a bounded staging buffer (<= 256 MiB); nothing below the first removed landmark moves.
+ * SLAM_E_BADARG (state unchanged): null handle, cnt < 0, cnt > 0 with ids == NULL, an id outside 1..N, a duplicate id.
+ * Ordered on the handle's stream behind everything enqueued before it (async updates included); synchronises. */
+int slam_ekf_remove_landmarks(slam_ekf_t h, const int32_t* ids, int cnt, int32_t* new_index);
 
 /* The filter's HIP stream (interop: event timing around its kernels). */
 int slam_pf_stream(slam_pf_t h, void** stream);

@@ -14,7 +14,7 @@ module SLAMHip
 
 export SlamState, EKFSlamState, set_state!, predict, update, add_features, associate,
        compute_association, predict_observation, mpi_to_pi,
-       ekf_predict!, ekf_update!, augment!, observe!, cov_block, cov_diag, landmark_blocks, gate_mode!, gate_info, state_written!, feature_ellipses, vehicle_ellipse,
+       ekf_predict!, ekf_update!, augment!, observe!, cov_block, cov_diag, landmark_blocks, gate_mode!, gate_info, state_written!, remove_features!, feature_ellipses, vehicle_ellipse,
        PFSlamState, set_pose!, init_landmarks!, pf_predict!, update_known!, step!, step_async!, step_async_batch!, flush!,
        resample!, mean_pose, weights, particles, pf_map, pf_best_particle, peer_blob, attach_peers!, peer_selftest, detach_peers!, comm_info
 
@@ -223,6 +223,21 @@ keeps beside the matrix (packed 2 x 2 blocks, variance bound, grid of means).  A
 function state_written!(s::EKFSlamState)
     check(ccall((:slam_ekf_state_written, libslamhip), Cint, (Ptr{Cvoid},), handle(s)))
     s
+end
+
+"""
+    remove_features!(s, ids) -> new_index::Vector{Int32}
+
+Map management (no counterpart in the reference, whose map only grows): the landmarks `ids` (1-based, any order) leave the
+map in place on the device -- x <- x[keep], cov <- cov[keep, keep], bit for bit; the others keep their order and are
+renumbered.  `new_index[j]` is the new id of old landmark j, 0 if it was removed (slam_ekf_remove_landmarks).
+"""
+function remove_features!(s::EKFSlamState, ids::AbstractVector{<:Integer})
+    new_index = zeros(Int32, nlandmarks(s))
+    rm = collect(Int32, ids)
+    check(ccall((:slam_ekf_remove_landmarks, libslamhip), Cint, (Ptr{Cvoid}, Ptr{Int32}, Cint, Ptr{Int32}),
+                handle(s), rm, length(rm), new_index))
+    new_index
 end
 
 "feature_ellipses(x, cov) of the browser monitor (sim/browser/wsserver.jl:72-85): 5 x N [cx; cy; rx; ry; phi], on the device."

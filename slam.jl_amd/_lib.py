@@ -105,6 +105,7 @@ SIGNATURES = {
     "slam_ekf_debug_stamps": (C.c_int, [_h, C.c_int, C.POINTER(C.c_uint64)]),
     "slam_ekf_state_written": (C.c_int, [_h]),
     "slam_ekf_copy_floor": (C.c_int, [_h, C.c_int, _dp]),
+    "slam_ekf_remove_landmarks": (C.c_int, [_h, _ip, C.c_int, _ip]),
     "slam_pf_create": (C.c_int, [C.POINTER(_h), C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_uint64]),
     "slam_pf_destroy": (C.c_int, [_h]),
     "slam_pf_set_pose": (C.c_int, [_h, _dp]),

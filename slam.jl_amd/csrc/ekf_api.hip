@@ -583,6 +583,52 @@ extern "C" int slam_ekf_state_written(slam_ekf_t h) {
     return launch_side_rebuild(h);      // the packed 2 x 2 diagonal blocks follow the matrix again
 }
 
+/* Map management (slamhip_diag.h): landmarks ids[] leave the map, x <- x[keep], P <- P[keep, keep] in place on the device
+ * (ekf_compact.hip).  Everything is validated on the host before anything is enqueued: an error leaves the state alone. */
+extern "C" int slam_ekf_remove_landmarks(slam_ekf_t h, const int32_t* ids, int cnt, int32_t* new_index) {
+    SLAM_RANGE();
+    ARG_CHECK(h != nullptr, "null handle");
+    ARG_CHECK(cnt >= 0, "cnt < 0");
+    ARG_CHECK(cnt == 0 || ids != nullptr, "ids is null");
+    const int N = h->N;
+    std::vector<char> gone((size_t)N + 1, 0);
+    for (int i = 0; i < cnt; ++i) {
+        ARG_CHECK(ids[i] >= 1 && ids[i] <= N, "landmark id out of range");
+        ARG_CHECK(!gone[ids[i]], "duplicate landmark id");
+        gone[ids[i]] = 1;
+    }
+    if (cnt == 0) {
+        if (new_index)
+            for (int j = 1; j <= N; ++j) new_index[j - 1] = j;
+        return SLAM_OK;
+    }
+    const int n_new = 3 + 2 * (N - cnt);
+    std::vector<int32_t> keep((size_t)n_new);
+    keep[0] = 0; keep[1] = 1; keep[2] = 2;
+    int first = 0, next = 0;                                // first removed landmark; survivors so far
+    for (int j = 1; j <= N; ++j) {
+        if (gone[j]) {
+            if (!first) first = j;
+            continue;
+        }
+        keep[3 + 2 * next] = 3 + 2 * (j - 1);
+        keep[4 + 2 * next] = 4 + 2 * (j - 1);
+        ++next;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    int rc;
+    if ((rc = launch_compact(h, keep.data(), n_new, 3 + 2 * (first - 1)))) return rc;
+    h->N = N - cnt;
+    if ((rc = zero_panels(h))) return rc;                   // panel rows >= n must be zero for the down-date
+    h->pmax_valid = 0;                                      // the pre-gate's variance bound belongs to the old map
+    h->grid_force = 1;                                      // the grid's items hold landmark indices: they have changed
+    h->grid_n_seen = h->N;
+    if ((rc = launch_side_rebuild(h))) return rc;           // the packed 2 x 2 diagonal blocks follow the renumbering
+    if (new_index)
+        for (int j = 1, k = 0; j <= N; ++j) new_index[j - 1] = gone[j] ? 0 : ++k;
+    return SLAM_OK;
+}
+
 extern "C" int slam_ekf_copy_floor(slam_ekf_t h, int reps, double out[2]) {
     SLAM_RANGE();
     ARG_CHECK(h != nullptr && out != nullptr, "null argument");

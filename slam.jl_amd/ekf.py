@@ -33,6 +33,7 @@ __all__ = [
     "observe",
     "SlamState", "EKFSlamState", "DeviceRef", "predict", "update", "add_features", "associate",
     "compute_association", "predict_observation", "mpi_to_pi", "ekf_predict_", "ekf_update_", "augment_",
+    "remove_features", "remove_features_", "removal_maps",
 ]
 
 _DTYPES = {"f32": (SLAM_F32, np.float32), "f64": (SLAM_F64, np.float64),
@@ -69,6 +70,26 @@ def _obs(z):
     if z.shape[0] != 2:
         raise ValueError("z must be 2 x nz")
     return np.ascontiguousarray(z.T)
+
+
+def removal_maps(N, ids):
+    """The two index maps of a landmark removal, as slam_ekf_remove_landmarks builds them on the host (restated here
+    for callers that renumber their own per-landmark tables, and for the CPU tests): ``keep`` (int32, 3 + 2 (N - cnt)
+    surviving 0-based state indices, ascending -- x[keep], P[keep][:, keep] is the reduced state) and ``new_index``
+    (int32, N entries: the new 1-based id of old landmark j at [j - 1], 0 if removed).  ``ids``: 1-based, any order;
+    ValueError for an id outside 1..N or a duplicate (the library: SLAM_E_BADARG)."""
+    ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+    if ids.size and (ids.min() < 1 or ids.max() > N):
+        raise ValueError("landmark id out of range")
+    gone = np.zeros(N, dtype=bool)
+    gone[ids - 1] = True
+    if int(gone.sum()) != ids.size:
+        raise ValueError("duplicate landmark id")
+    left = np.flatnonzero(~gone)
+    keep = np.concatenate([np.arange(3), np.stack([3 + 2 * left, 4 + 2 * left], axis=1).reshape(-1)]).astype(np.int32)
+    new_index = np.zeros(N, dtype=np.int32)
+    new_index[left] = np.arange(1, left.size + 1, dtype=np.int32)
+    return keep, new_index
 
 
 def mpi_to_pi(phi):
@@ -335,6 +356,17 @@ class EKFSlamState(SlamState):
         r = _small(R)
         check(lib.slam_ekf_augment(self._h, _ptr(zp), zp.shape[0], _ptr(r)))
 
+    def remove_landmarks(self, ids):
+        """Take the landmarks ``ids`` (1-based, as idf; any order) out of the map, in place on the device
+        (slam_ekf_remove_landmarks): x <- x[keep], P <- P[keep, keep] bit for bit, the others keep their order and are
+        renumbered 1..N - len(ids).  Returns ``new_index`` (int32, length N_old): the new id of old landmark j at
+        [j - 1], 0 if it was removed."""
+        ids = np.ascontiguousarray(np.asarray(ids, dtype=np.int32).reshape(-1))
+        new_index = np.zeros(self.N, dtype=np.int32)
+        check(lib.slam_ekf_remove_landmarks(self._h, _ptr(ids, C.c_int32) if ids.size else None, int(ids.size),
+                                            _ptr(new_index, C.c_int32) if new_index.size else None))
+        return new_index
+
     def observe(self, z, R, gate1, gate2, form="cholesky"):
         """associate -> update -> add_features (sim/ekfslam-sim.jl:114-120) in one library call with no host
         round trip between the gating and the update.  Returns the association vector
@@ -515,3 +547,14 @@ def ekf_update_(state, z, R, idf, form="cholesky"):
 def augment_(state, z, R):
     state.add_features(z, R)
     return state
+
+
+# map management: no counterpart in the reference (its map only grows)
+def remove_features(state: EKFSlamState, ids):
+    """Remove the landmarks ``ids`` (1-based) from the map -> ``new_index`` (see EKFSlamState.remove_landmarks)."""
+    return _state_of(state).remove_landmarks(ids)
+
+
+def remove_features_(state, ids):
+    """In-place name (Julia: ``remove_features!``); returns the index map as well."""
+    return _state_of(state).remove_landmarks(ids)

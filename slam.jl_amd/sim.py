@@ -138,6 +138,7 @@ class SimLog:
     obs_steps: list = field(default_factory=list)       # predict-step index of each observation step
     observations: list = field(default_factory=list)    # z (2 x nz) per observation step
     assoc: list = field(default_factory=list)           # (idf list, n_new) per observation step
+    pruned: list = field(default_factory=list)          # (observation step, removed ids) per removal (sim(prune_after=k))
     true_track: list = field(default_factory=list)
     slam_track: list = field(default_factory=list)
 
@@ -161,12 +162,17 @@ def default_QR():
 
 
 def sim(filt, waypoints: np.ndarray, landmarks: np.ndarray, seed: int, nlaps: int = 2,
-        max_steps: int = 100000, monitor=None, fused: bool = False) -> SimLog:
+        max_steps: int = 100000, monitor=None, fused: bool = False, prune_after=None) -> SimLog:
     """The loop of sim/ekfslam-sim.jl:80-141 without sleep/pause.
 
     ``filt`` must already hold the initial state (x = initial pose, P = 0).
     ``fused``: use ``filt.observe`` (associate + update + add_features in one library call,
     same results) instead of the three calls of :114-120.
+    ``prune_after``: None (default) is the reference's loop, whose map only grows.  An integer k (no counterpart in the
+    reference): a landmark that has been matched only by the observation that created it and is not matched in the k
+    observation steps after its creation is removed with ``filt.remove_landmarks(ids) -> new_index``.  The per-landmark
+    counters live here on the host (the association comes back to the host anyway) and are renumbered through
+    ``new_index``; removals are recorded in ``log.pruned`` with the ids they had at that moment.
     """
     rng = np.random.default_rng(seed)
     Q, R = default_QR()
@@ -174,6 +180,8 @@ def sim(filt, waypoints: np.ndarray, landmarks: np.ndarray, seed: int, nlaps: in
     log = SimLog()
     dtsum = 0.0
     nsteps = 0
+    born = np.zeros(0, dtype=np.int64)      # prune_after: observation step that created landmark j (at [j - 1]) ...
+    hits = np.zeros(0, dtype=np.int64)      # ... and its matches since
     while vehicle.waypoint_id != 0 and nsteps < max_steps:
         steer(vehicle, waypoints, D_MIN, DT)                              # :85
         if vehicle.waypoint_id == 0 and nlaps > 1:                        # :88-91
@@ -199,6 +207,18 @@ def sim(filt, waypoints: np.ndarray, landmarks: np.ndarray, seed: int, nlaps: in
             log.obs_steps.append(nsteps)
             log.observations.append(np.array(z))
             log.assoc.append((np.asarray(idf).reshape(-1).tolist(), int(np.asarray(zn).reshape(2, -1).shape[1])))
+            if prune_after is not None:
+                t = len(log.obs_steps) - 1
+                np.add.at(hits, np.asarray(idf, dtype=np.int64).reshape(-1) - 1, 1)
+                nn = log.assoc[-1][1]
+                born = np.concatenate([born, np.full(nn, t, dtype=np.int64)])
+                hits = np.concatenate([hits, np.zeros(nn, dtype=np.int64)])
+                stale = np.flatnonzero((hits == 0) & (t - born >= int(prune_after)))
+                if stale.size:
+                    new_index = np.asarray(filt.remove_landmarks(stale + 1))
+                    log.pruned.append((t, (stale + 1).tolist()))
+                    left = new_index > 0
+                    born, hits = born[left], hits[left]
         nsteps += 1
         log.true_track.append(np.array(vehicle.pose))
         log.slam_track.append(np.array(filt.pose()))
