@@ -845,8 +845,12 @@ __global__ __launch_bounds__(256) void pf_auto_resample_kernel(T* pose0, T* pose
     const double total = s_off[nb];
     const double target = ((double)(first + p) + ctl->u0) / (double)n_global * total;
     // first j with cdf[j] + offset(block of j) >= target, in two levels: the block out of LDS (the last element of block b
-    // has exactly the value s_off[b + 1] = s_off[b] + bsum[b]), then ten steps inside it -- the same index as the plain
-    // binary search of pf_ancestor_kernel over all n
+    // has exactly the value s_off[b + 1] = s_off[b] + bsum[b]), then ten steps inside it.  The same index as the plain
+    // binary search of pf_ancestor_kernel over all n WHENEVER no target falls on a descent of the stored cdf: the values are
+    // not monotone (block_scan1024, pf_device.h: one-ulp descents, 12 to 17 of them on 5000 half-dead weights), and a target
+    // inside such a descent is found at different indices by different probe orders.  The targets of a resampling hit one with
+    // a probability of the order of n * descents * 2^-52; the CPU model of both searches (tests/resample_ref.py,
+    // tests/test_resample_ref_cpu.py) pins the descent counts and shows 0 differing slots on every scene of the suite.
     int bl = 0, bh = nb - 1;
     while (bl < bh) {
         const int bm = (bl + bh) >> 1;
@@ -856,7 +860,8 @@ __global__ __launch_bounds__(256) void pf_auto_resample_kernel(T* pose0, T* pose
     if (hi > n_global - 1) hi = n_global - 1;
     const double bo = s_off[bl];
     // first j in [lo, hi] with cdf[j] + bo >= target, else hi -- what ten dependent halvings found, in THREE rounds of independent
-    // probes (strides 128, 16, 1: the values are monotone, so the first probe that reaches the target brackets the answer)
+    // probes (strides 128, 16, 1: the first probe that reaches the target brackets the answer -- exactly so where the values
+    // around the target are monotone, see above for the one-ulp descents where they are not)
     {
         const int64_t last = hi;
 #pragma unroll

@@ -880,8 +880,12 @@ __device__ __forceinline__ T ld_sc1(const T* p) {
 // Inclusive scan of one double per thread over a 1024-thread workgroup (the cdf blocks of the systematic resampling): inside a
 // wave by shuffles (Hillis-Steele over 64 lanes), the waves' totals added in wave order -- ONE barrier instead of the twenty of
 // a Hillis-Steele scan over 1024 LDS words (round 4: the conditional cdf kernel 5.0 -> ~2 us).  Both cdf kernels (the legacy one
-// and the auto mode's) use it, so their ancestors stay identical; the order of additions is fixed, hence the same cdf for any
-// number of ranks.  sh16: 16 doubles of LDS.
+// and the auto mode's) use it, so they store the SAME cdf bit for bit; the order of additions is fixed, hence the same cdf for any
+// number of ranks.  Neighbouring entries are summed along different trees, so the stored cdf is NOT monotone: it descends by one
+// ulp in places (12 to 17 places on 5000 weights of which half are dead, tests/test_resample_ref_cpu.py).  What holds: the
+// legacy binary search and the auto mode's probe search return identical ancestors whenever no target falls on such a descent,
+// and every ancestor is the exact one wherever the target is further than the scan's rounding from a cdf step
+// (tests/resample_ref.py).  sh16: 16 doubles of LDS.
 __device__ __forceinline__ double block_scan1024(double v, double* sh16) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
