@@ -1,6 +1,6 @@
 /* slamhip_diag.h -- the MEASUREMENT and introspection entry points of libslamhip.so: event timing of the kernels, phase
  * stamps, the copy floor of the down-date, which form of the gating ran, what the exchange between the ranks of a sharded
- * filter saw, the read-outs of the particle filter's state (its map, one particle) and the EKF's map management (landmark removal) that
+ * filter saw, the read-outs of the particle filter's state (its map, one particle), its fused unknown-correspondence step and the EKF's map management (landmark removal) that
  * the reference has no counterpart for.  Nothing here is part of the drop-in boundary (include/slamhip.h: what the reference's module surface maps
  * onto); bench.py, the tests and the profiling tools use them.  Same conventions: extern "C", int status codes. */
 #ifndef SLAMHIP_DIAG_H
@@ -111,6 +111,21 @@ int slam_pf_get_map(slam_pf_t h, const int32_t* ids, int cnt, double* out);
 /* Local particle `idx` (-1: the one with the largest log-weight, the lowest index on a tie): its global id, log-weight, pose
  * and, if lm != NULL, its nl x 5 landmark records {x, y, Pxx, Pxy, Pyy} (row-major, double).  gid, logw, pose may be NULL. */
 int slam_pf_get_particle(slam_pf_t h, int64_t idx, int64_t* gid, double* logw, double pose[3], double* lm);
+
+/* ---- FastSLAM, unknown correspondences ---------------------------------------------------------------------------------------
+ * predict + per-particle association + updates / new landmarks + local weight statistics as ONE sweep over the particles:
+ * slam_pf_predict, slam_pf_update_unknown and slam_pf_weight_stats in one kernel, for m <= 64 (range, bearing) pairs.
+ * Every observation is associated against the map as it is after the predict and before any of this call's updates; the
+ * updates then run in observation order (a second observation of a slot sees the first one's update; a new landmark goes to the
+ * particle's lowest unused slot, none left: dropped).  m <= 16: particles, decisions and statistics are those of the three
+ * calls bit for bit (the same RNG step is consumed, a pending normalisation shift is honoured the same way).  m == 0: predict
+ * and statistics only.  d_assoc (device, [m][n] int32, may be NULL): slot >= 0 matched, -1 new, -2 dropped.
+ * out = {max logw, sum, sum2} as slam_pf_weight_stats.  SLAM_E_BADARG (state and RNG step unchanged): m < 0, m > 64, z == NULL
+ * with m > 0.  Leaves the auto mode, materialises lazily resampled maps, is collective while peers are attached (all as
+ * slam_pf_update_unknown); synchronises. */
+int slam_pf_step_unknown(slam_pf_t h, double V, double G, double wheelbase, const double Q[4], double dt,
+                         const double* z, int m, const double R[4], double gate1, double gate2,
+                         int32_t* d_assoc, double out[3]);
 
 #ifdef __cplusplus
 }

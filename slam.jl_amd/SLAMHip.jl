@@ -15,7 +15,7 @@ module SLAMHip
 export SlamState, EKFSlamState, set_state!, predict, update, add_features, associate,
        compute_association, predict_observation, mpi_to_pi,
        ekf_predict!, ekf_update!, augment!, observe!, cov_block, cov_diag, landmark_blocks, gate_mode!, gate_info, state_written!, remove_features!, feature_ellipses, vehicle_ellipse,
-       PFSlamState, set_pose!, init_landmarks!, pf_predict!, update_known!, step!, step_async!, step_async_batch!, flush!,
+       PFSlamState, set_pose!, init_landmarks!, pf_predict!, update_known!, step!, step_async!, step_async_batch!, step_unknown!, flush!,
        resample!, mean_pose, weights, particles, pf_map, pf_best_particle, peer_blob, attach_peers!, peer_selftest, detach_peers!, comm_info
 
 const libslamhip = get(ENV, "SLAMHIP_LIB", joinpath(@__DIR__, "libslamhip.so"))
@@ -408,6 +408,23 @@ function update_known!(s::PFSlamState, z::AbstractMatrix, ids, R::AbstractMatrix
     check(ccall((:slam_pf_update_known, libslamhip), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Int32}, Cint, Ptr{Cdouble}),
                 s.handle, pairs64(z), Vector{Int32}(vec(collect(ids))), m, colmajor4(R)))
     s
+end
+
+"""
+    step_unknown!(state, V, G, wheelbase, Q, dt, z, R, gate1, gate2) -> [max logw, sum, sum2]
+
+Predict, per-particle association of the (range, bearing) pairs `z` (2 x m, m <= 64, UNKNOWN correspondences) against each
+particle's own landmarks, updates / new landmarks and the local weight statistics as one sweep (slam_pf_step_unknown).
+"""
+function step_unknown!(s::PFSlamState, V::Real, G::Real, wheelbase::Real, Q::AbstractMatrix, dt::Real, z::AbstractMatrix,
+                       R::AbstractMatrix, gate1::Real, gate2::Real)
+    out = zeros(Float64, 3)
+    check(ccall((:slam_pf_step_unknown, libslamhip), Cint,
+                (Ptr{Cvoid}, Cdouble, Cdouble, Cdouble, Ptr{Cdouble}, Cdouble, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cdouble, Cdouble,
+                 Ptr{Int32}, Ptr{Cdouble}),
+                s.handle, V, G, wheelbase, colmajor4(Q), dt, pairs64(z), size(z, 2), colmajor4(R), gate1, gate2,
+                Ptr{Int32}(C_NULL), out))
+    out
 end
 
 """

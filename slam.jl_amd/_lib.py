@@ -153,6 +153,8 @@ SIGNATURES = {
     "slam_pf_map_sums": (C.c_int, [_h, _ip, C.c_int, _dp]),
     "slam_pf_get_map": (C.c_int, [_h, _ip, C.c_int, _dp]),
     "slam_pf_get_particle": (C.c_int, [_h, C.c_int64, C.POINTER(C.c_int64), _dp, _dp, _dp]),
+    "slam_pf_step_unknown": (C.c_int, [_h, C.c_double, C.c_double, C.c_double, _dp, C.c_double, _dp, C.c_int, _dp, C.c_double,
+                                       C.c_double, C.c_void_p, _dp]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -1,5 +1,5 @@
 // pf_internal.h -- the FastSLAM particle path: state, control blocks and the host-side pieces shared by its translation
-// units (pf_legacy.hip: the rank-local kernels and entry points; pf_auto.hip: the step without the host; pf_peers.hip: the
+// units (pf_legacy.hip: the rank-local kernels and entry points; pf_unknown.hip: the unknown-correspondence step; pf_auto.hip: the step without the host; pf_peers.hip: the
 // sharding behind the C ABI; pf_map.hip: the map and particle read-outs).  Device code common to the kernels: pf_device.h.
 #pragma once
 #include <stdlib.h>
@@ -260,6 +260,9 @@ const char* pf_error_text(long long code);
 // pf_legacy.hip
 double pf_take_pending(slam_pf* h);        // the normalisation shift slam_pf_normalize deferred (and forget it)
 int pf_materialise(slam_pf* h);            // every landmark to (buffer h->cur, identity table); collective with peers attached
+int pf_stage(slam_pf* h, const double* z, const int32_t* ids, int m, const double** d_z, const int32_t** d_i);   // observations into the next pinned staging slot
+int pf_stage_done(slam_pf* h);             // record the slot's event behind the kernel that reads it
+int pf_fold_and_read(slam_pf* h, int relative_to_max, double out[7]);   // fold the block partials in d_part, bring the seven numbers to the host
 // pf_peers.hip
 void pf_detach_peers_impl(slam_pf* h);
 void pf_announce_gone(slam_pf* h);         // "this rank is going away" into every peer's inbox (destroy of an attached handle)

@@ -850,7 +850,7 @@ static int pf_flush_pending(slam_pf* h) {
 // Stage m observations (ids recoded 0-based with the first-sighting flag) into the next staging slot and queue
 // the copies; returns the slot's device addresses.  No stream synchronisation: a slot is reused only after the
 // event behind its previous copies has fired.
-static int pf_stage(slam_pf* h, const double* z, const int32_t* ids, int m, const double** d_z, const int32_t** d_i) {
+int pf_stage(slam_pf* h, const double* z, const int32_t* ids, int m, const double** d_z, const int32_t** d_i) {
     const int slot = h->stage_slot;
     h->stage_slot ^= 1;
     if (h->stage_used[slot]) HIP_TRY(hipEventSynchronize(h->stage_ev[slot]));
@@ -891,7 +891,7 @@ static int pf_stage(slam_pf* h, const double* z, const int32_t* ids, int m, cons
     return SLAM_OK;
 }
 
-static int pf_stage_done(slam_pf* h) {
+int pf_stage_done(slam_pf* h) {
     HIP_TRY(hipEventRecord(h->stage_ev[h->stage_last], h->stream));
     h->stage_used[h->stage_last] = 1;
     return SLAM_OK;
@@ -949,7 +949,7 @@ static int pf_wait_stats(slam_pf* h, double out[7]) {
     return SLAM_OK;
 }
 
-static int pf_fold_and_read(slam_pf* h, int relative_to_max, double out[7]) {
+int pf_fold_and_read(slam_pf* h, int relative_to_max, double out[7]) {
     h->out_seq += 1;
     hipLaunchKernelGGL(pf_fold_kernel, dim3(1), dim3(256), 0, h->stream, (const double*)h->d_part, h->red_blocks,
                        relative_to_max, h->d_out, h->h_out_dev, h->out_seq);

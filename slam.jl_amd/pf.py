@@ -208,6 +208,26 @@ class PFShard:
             self.sync()
         return assoc
 
+    def step_unknown_fused(self, V, G, wheelbase, Q, dt, z, R, gate1, gate2, want_assoc=False):
+        """predict + update_unknown + weight_stats as ONE sweep over the particles (slam_pf_step_unknown), for up to 64
+        observations; with at most 16 the same particles, decisions and statistics bit for bit.  Returns
+        (gmax, s1, s2), or ((gmax, s1, s2), assoc) with ``want_assoc`` (int32 torch tensor [m, n] on the device: slot >= 0
+        matched, -1 new, -2 dropped)."""
+        zp = _obs(z)
+        m = zp.shape[0]
+        q, r = _small(Q), _small(R)
+        assoc = None
+        ptr = None
+        if want_assoc:
+            import torch
+            assoc = torch.empty((m, self.n), dtype=torch.int32, device=self.device)
+            ptr = C.c_void_p(assoc.data_ptr()) if m else None
+        out = np.empty(3)
+        check(lib.slam_pf_step_unknown(self._h, float(V), float(G), float(wheelbase), _ptr(q), float(dt), _ptr(zp), m, _ptr(r),
+                                       float(gate1), float(gate2), ptr, _ptr(out)))
+        stats = (float(out[0]), float(out[1]), float(out[2]))      # (the call synchronises: assoc is complete)
+        return (stats, assoc) if want_assoc else stats
+
     def weight_stats(self):
         out = np.empty(3)
         check(lib.slam_pf_weight_stats(self._h, _ptr(out)))
@@ -815,6 +835,16 @@ class FastSLAM:
         self.predict(V, G, wheelbase, Q, dt)
         self.shard.update_unknown(z, R, gate1, gate2)
         neff = self.normalize()
+        do = force_resample if force_resample is not None else (neff < self.neff_frac * self.shard.n_global)
+        if do:
+            self.resample()
+        return neff, bool(do)
+
+    def step_unknown_fused(self, V, G, wheelbase, Q, dt, z, R, gate1, gate2, force_resample=None):
+        """``step_unknown`` with predict, association + updates and the weight statistics as ONE sweep over the particles
+        (shard.step_unknown_fused), for up to 64 observations per step.  Returns (Neff, resampled?)."""
+        self._gmax_norm = None
+        neff = self.normalize(self.shard.step_unknown_fused(V, G, wheelbase, Q, dt, z, R, gate1, gate2))
         do = force_resample if force_resample is not None else (neff < self.neff_frac * self.shard.n_global)
         if do:
             self.resample()
