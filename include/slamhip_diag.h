@@ -1,6 +1,6 @@
 /* slamhip_diag.h -- the MEASUREMENT and introspection entry points of libslamhip.so: event timing of the kernels, phase
  * stamps, the copy floor of the down-date, which form of the gating ran, what the exchange between the ranks of a sharded
- * filter saw, the read-outs of the particle filter's state (its map, one particle), its fused unknown-correspondence step and the EKF's map management (landmark removal) that
+ * filter saw, the read-outs of the particle filter's state (its map, one particle), its fused unknown-correspondence step and the EKF's map management (landmark removal, duplicate search and merge) that
  * the reference has no counterpart for.  Nothing here is part of the drop-in boundary (include/slamhip.h: what the reference's module surface maps
  * onto); bench.py, the tests and the profiling tools use them.  Same conventions: extern "C", int status codes. */
 #ifndef SLAMHIP_DIAG_H
@@ -68,6 +68,34 @@ int slam_ekf_copy_floor(slam_ekf_t h, int reps, double out[2]);
  * SLAM_E_BADARG (state unchanged): null handle, cnt < 0, cnt > 0 with ids == NULL, an id outside 1..N, a duplicate id.
  * Ordered on the handle's stream behind everything enqueued before it (async updates included); synchronises. */
 int slam_ekf_remove_landmarks(slam_ekf_t h, const int32_t* ids, int cnt, int32_t* new_index);
+
+/* Duplicate landmarks.  Gated nearest-neighbour association enters a landmark a second time when the pose has drifted past
+ * gate2 (the end of a long loop); from then on the map holds two landmarks for one feature.  For a < b (1-based), with
+ * f(j) = 3 + 2 (j - 1):  delta = x[f(b) : f(b) + 2] - x[f(a) : f(a) + 2],  D = P_aa + P_bb - P_ab - P_ab' (the covariance of the
+ * difference; evaluated in double from the stored values and symmetrised),  d2 = delta' inv(D) delta.  The pair is a duplicate
+ * when D is positive definite as computed (D00 > 0 and det > 0) and d2 < gate.
+ * *count = the number of duplicate pairs of the whole map; pairs receives the first min(count, cap) of them as (a, b), a < b,
+ * in ascending lexicographic order (the same from call to call); pairs may be NULL when cap == 0.
+ * A pair is first rejected from the means and the packed diagonal blocks alone (|delta|^2 >= 2 gate (tr P_aa + tr P_bb), which no
+ * duplicate satisfies while the pair's joint covariance is positive semi-definite as stored); only the others read P_ab.
+ * SLAM_E_BADARG: null handle, null count, cap < 0, cap > 0 with pairs == NULL, gate not finite or <= 0.
+ * Ordered on the handle's stream behind everything enqueued before it; synchronises; the state is not changed. */
+int slam_ekf_find_duplicates(slam_ekf_t h, double gate, int32_t* pairs, int cap, int* count);
+
+/* Merge landmarks: pair p = (pairs[2p], pairs[2p + 1]) = (a_p, b_p) says "a_p and b_p are one point", the linear measurement
+ * m_a - m_b = 0 with noise Rc (symmetric positive semi-definite 2 x 2, column-major as R; NULL = zero, the exact constraint).
+ * All pairs of a call are ONE update in the reference's Cholesky form (src/ekf.jl:67-75): one pass over P however many pairs.
+ * Then every b_p (the landmark named SECOND, whichever id is larger) is removed exactly as slam_ekf_remove_landmarks removes
+ * it; the survivors keep their order.  new_index (may be NULL; N_old entries): as for removal for every survivor, and for a
+ * removed b_p the NEW id of a_p.  cnt == 0: nothing happens.
+ * SLAM_E_BADARG (state unchanged, decided before anything is enqueued): null handle, cnt < 0, cnt > SLAM_MERGE_MAX, cnt > 0 with
+ * pairs == NULL, an id outside 1..N, a == b, a landmark in more than one pair of the call (merge a chain by calling again), Rc not
+ * symmetric or with a negative diagonal.  SLAM_E_NOTPD: S is not positive definite (two landmarks already perfectly
+ * correlated, with Rc = 0): state unchanged, nothing removed.
+ * Ordered on the handle's stream behind everything enqueued before it (async updates included, whose deferred status stays
+ * pending for slam_ekf_sync); synchronises. */
+#define SLAM_MERGE_MAX 8      /* pairs per call: k = 16, one 16-column chunk of the down-date */
+int slam_ekf_merge_landmarks(slam_ekf_t h, const int32_t* pairs, int cnt, const double Rc[4], int32_t* new_index);
 
 /* The filter's HIP stream (interop: event timing around its kernels). */
 int slam_pf_stream(slam_pf_t h, void** stream);

@@ -14,7 +14,7 @@ module SLAMHip
 
 export SlamState, EKFSlamState, set_state!, predict, update, add_features, associate,
        compute_association, predict_observation, mpi_to_pi,
-       ekf_predict!, ekf_update!, augment!, observe!, cov_block, cov_diag, landmark_blocks, gate_mode!, gate_info, state_written!, remove_features!, feature_ellipses, vehicle_ellipse,
+       ekf_predict!, ekf_update!, augment!, observe!, cov_block, cov_diag, landmark_blocks, gate_mode!, gate_info, state_written!, remove_features!, find_duplicates, merge_landmarks!, feature_ellipses, vehicle_ellipse,
        PFSlamState, set_pose!, init_landmarks!, pf_predict!, update_known!, step!, step_async!, step_async_batch!, step_unknown!, flush!,
        resample!, mean_pose, weights, particles, pf_map, pf_best_particle, peer_blob, attach_peers!, peer_selftest, detach_peers!, comm_info
 
@@ -237,6 +237,39 @@ function remove_features!(s::EKFSlamState, ids::AbstractVector{<:Integer})
     rm = collect(Int32, ids)
     check(ccall((:slam_ekf_remove_landmarks, libslamhip), Cint, (Ptr{Cvoid}, Ptr{Int32}, Cint, Ptr{Int32}),
                 handle(s), rm, length(rm), new_index))
+    new_index
+end
+
+"""
+    find_duplicates(s, gate; cap = 1024) -> (pairs::Matrix{Int32}, count)
+
+Landmarks entered twice (slam_ekf_find_duplicates): the pairs (a, b), a < b, whose difference has a Mahalanobis distance below
+`gate` under D = P_aa + P_bb - P_ab - P_ab'.  `pairs` is 2 x min(count, cap), one pair per column, ascending; `count` is the
+number of pairs in the whole map.  The state is not changed.
+"""
+function find_duplicates(s::EKFSlamState, gate::Real; cap::Integer = 1024)
+    pairs = zeros(Int32, 2, max(cap, 0))
+    count = Ref{Cint}(0)
+    check(ccall((:slam_ekf_find_duplicates, libslamhip), Cint, (Ptr{Cvoid}, Cdouble, Ptr{Int32}, Cint, Ref{Cint}),
+                handle(s), gate, pairs, cap, count))
+    pairs[:, 1:min(Int(count[]), max(cap, 0))], Int(count[])
+end
+
+"""
+    merge_landmarks!(s, pairs; Rc = nothing) -> new_index::Vector{Int32}
+
+Fuse the landmarks of every column (a, b) of `pairs` (2 x cnt, cnt <= 8, no landmark twice) into one: the constraint
+m_a - m_b = 0 with noise `Rc` (2 x 2, `nothing` = exact) as one Cholesky-form update, then b leaves the map as
+`remove_features!` removes it (slam_ekf_merge_landmarks).  `new_index[j]` is the new id of old landmark j; for a removed b
+the new id of its a.
+"""
+function merge_landmarks!(s::EKFSlamState, pairs::AbstractMatrix{<:Integer}; Rc = nothing)
+    size(pairs, 1) == 2 || throw(ArgumentError("pairs must be 2 x cnt"))
+    new_index = zeros(Int32, nlandmarks(s))
+    pr = collect(Int32, pairs)
+    rc = Rc === nothing ? C_NULL : collect(Float64, Rc)      # column-major double[4], as R
+    check(ccall((:slam_ekf_merge_landmarks, libslamhip), Cint, (Ptr{Cvoid}, Ptr{Int32}, Cint, Ptr{Cdouble}, Ptr{Int32}),
+                handle(s), pr, size(pr, 2), rc, new_index))
     new_index
 end
 

@@ -25,6 +25,7 @@ SLAM_PF_HALTED = 1
 SLAM_PF_PEER_BLOB_BYTES = 4096
 SLAM_F32, SLAM_F64 = 0, 1
 SLAM_FORM_CHOLESKY, SLAM_FORM_JOSEPH = 0, 1
+SLAM_MERGE_MAX = 8
 KERNEL_IDS = {"gate": 0, "gate_final": 1, "predict": 2, "augment": 3, "pht": 4, "factor": 5, "w1": 6, "syrk": 7}
 
 _ERRNAMES = {SLAM_E_BADARG: "SLAM_E_BADARG", SLAM_E_CAPACITY: "SLAM_E_CAPACITY", SLAM_E_NOTPD: "SLAM_E_NOTPD",
@@ -106,6 +107,8 @@ SIGNATURES = {
     "slam_ekf_state_written": (C.c_int, [_h]),
     "slam_ekf_copy_floor": (C.c_int, [_h, C.c_int, _dp]),
     "slam_ekf_remove_landmarks": (C.c_int, [_h, _ip, C.c_int, _ip]),
+    "slam_ekf_find_duplicates": (C.c_int, [_h, C.c_double, _ip, C.c_int, C.POINTER(C.c_int)]),
+    "slam_ekf_merge_landmarks": (C.c_int, [_h, _ip, C.c_int, _dp, _ip]),
     "slam_pf_create": (C.c_int, [C.POINTER(_h), C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_uint64]),
     "slam_pf_destroy": (C.c_int, [_h]),
     "slam_pf_set_pose": (C.c_int, [_h, _dp]),

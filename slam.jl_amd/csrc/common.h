@@ -199,6 +199,8 @@ int launch_pack(slam_ekf* h, const void* d_src, int lds, int n, int cf, int ncol
 int launch_unpack(slam_ekf* h, void* d_dst, int ldd, int n, int cf, int ncols);       // columns [cf, cf + ncols) of the full symmetric matrix -> d_dst (that band, column-major)
 int launch_side_rebuild(slam_ekf* h);    // Pside <- the entries of the matrix itself (slam_ekf_state_written)
 int launch_compact(slam_ekf* h, const int32_t* keep_host, int n_new, int f0);   // x <- x[keep], P <- P[keep, keep] in place (ekf_compact.hip); h->N: the old count
+int launch_find_duplicates(slam_ekf* h, double gate, int32_t* pairs_out, int cap, int* count);   // every pair inside the gate, sorted (ekf_merge.hip); synchronises
+int launch_merge_update(slam_ekf* h, const int32_t* keep, const int32_t* gone, int cnt, const double Rc[4]);   // "keep[p] and gone[p] are one point" as one Cholesky-form update (ekf_merge.hip)
 int launch_copy_floor(slam_ekf* h, int reps, double out[2]);   // bare read + rewrite of the stored tiles, timed (ekf_syrk.hip)
 int launch_predict(slam_ekf* h, double v, double g, double w, const double Q[4], double dt);
 int launch_augment(slam_ekf* h, int nn, const double R[4], const double* zn_dev);   // zn already on the device (obsbuf or znbuf)

@@ -583,25 +583,10 @@ extern "C" int slam_ekf_state_written(slam_ekf_t h) {
     return launch_side_rebuild(h);      // the packed 2 x 2 diagonal blocks follow the matrix again
 }
 
-/* Map management (slamhip_diag.h): landmarks ids[] leave the map, x <- x[keep], P <- P[keep, keep] in place on the device
- * (ekf_compact.hip).  Everything is validated on the host before anything is enqueued: an error leaves the state alone. */
-extern "C" int slam_ekf_remove_landmarks(slam_ekf_t h, const int32_t* ids, int cnt, int32_t* new_index) {
-    SLAM_RANGE();
-    ARG_CHECK(h != nullptr, "null handle");
-    ARG_CHECK(cnt >= 0, "cnt < 0");
-    ARG_CHECK(cnt == 0 || ids != nullptr, "ids is null");
+// The landmarks marked in gone[1 .. N] (cnt of them, cnt >= 1) leave the map: x <- x[keep], P <- P[keep, keep] in place on the
+// device (ekf_compact.hip), then everything kept beside the matrix follows.  new_index as slam_ekf_remove_landmarks documents it.
+static int remove_marked(slam_ekf* h, const std::vector<char>& gone, int cnt, int32_t* new_index) {
     const int N = h->N;
-    std::vector<char> gone((size_t)N + 1, 0);
-    for (int i = 0; i < cnt; ++i) {
-        ARG_CHECK(ids[i] >= 1 && ids[i] <= N, "landmark id out of range");
-        ARG_CHECK(!gone[ids[i]], "duplicate landmark id");
-        gone[ids[i]] = 1;
-    }
-    if (cnt == 0) {
-        if (new_index)
-            for (int j = 1; j <= N; ++j) new_index[j - 1] = j;
-        return SLAM_OK;
-    }
     const int n_new = 3 + 2 * (N - cnt);
     std::vector<int32_t> keep((size_t)n_new);
     keep[0] = 0; keep[1] = 1; keep[2] = 2;
@@ -626,6 +611,87 @@ extern "C" int slam_ekf_remove_landmarks(slam_ekf_t h, const int32_t* ids, int c
     if ((rc = launch_side_rebuild(h))) return rc;           // the packed 2 x 2 diagonal blocks follow the renumbering
     if (new_index)
         for (int j = 1, k = 0; j <= N; ++j) new_index[j - 1] = gone[j] ? 0 : ++k;
+    return SLAM_OK;
+}
+
+/* Map management (slamhip_diag.h): landmarks ids[] leave the map, x <- x[keep], P <- P[keep, keep] in place on the device
+ * (ekf_compact.hip).  Everything is validated on the host before anything is enqueued: an error leaves the state alone. */
+extern "C" int slam_ekf_remove_landmarks(slam_ekf_t h, const int32_t* ids, int cnt, int32_t* new_index) {
+    SLAM_RANGE();
+    ARG_CHECK(h != nullptr, "null handle");
+    ARG_CHECK(cnt >= 0, "cnt < 0");
+    ARG_CHECK(cnt == 0 || ids != nullptr, "ids is null");
+    const int N = h->N;
+    std::vector<char> gone((size_t)N + 1, 0);
+    for (int i = 0; i < cnt; ++i) {
+        ARG_CHECK(ids[i] >= 1 && ids[i] <= N, "landmark id out of range");
+        ARG_CHECK(!gone[ids[i]], "duplicate landmark id");
+        gone[ids[i]] = 1;
+    }
+    if (cnt == 0) {
+        if (new_index)
+            for (int j = 1; j <= N; ++j) new_index[j - 1] = j;
+        return SLAM_OK;
+    }
+    return remove_marked(h, gone, cnt, new_index);
+}
+
+/* Map management (slamhip_diag.h): every pair of landmarks whose difference lies inside the gate (ekf_merge.hip). */
+extern "C" int slam_ekf_find_duplicates(slam_ekf_t h, double gate, int32_t* pairs, int cap, int* count) {
+    SLAM_RANGE();
+    ARG_CHECK(h != nullptr, "null handle");
+    ARG_CHECK(count != nullptr, "count is null");
+    ARG_CHECK(cap >= 0, "cap < 0");
+    ARG_CHECK(cap == 0 || pairs != nullptr, "pairs is null");
+    ARG_CHECK(gate > 0.0 && gate <= 1.79769313486231570815e308, "gate must be finite and positive");
+    HIP_TRY(hipSetDevice(h->device));
+    return launch_find_duplicates(h, gate, pairs, cap, count);
+}
+
+/* Map management (slamhip_diag.h): "pairs[2p] and pairs[2p + 1] are one point" as ONE Cholesky-form update, then the second
+ * landmark of every pair leaves the map.  Validated on the host before anything is enqueued; the stages after the
+ * factorisation skip themselves on the device when S is not positive definite, and the removal is not started. */
+extern "C" int slam_ekf_merge_landmarks(slam_ekf_t h, const int32_t* pairs, int cnt, const double Rc[4], int32_t* new_index) {
+    SLAM_RANGE();
+    ARG_CHECK(h != nullptr, "null handle");
+    ARG_CHECK(cnt >= 0 && cnt <= SLAM_MERGE_MAX, "cnt outside 0 .. SLAM_MERGE_MAX");
+    ARG_CHECK(cnt == 0 || pairs != nullptr, "pairs is null");
+    const int N = h->N;
+    std::vector<char> used((size_t)N + 1, 0), gone((size_t)N + 1, 0);
+    int32_t keep_id[SLAM_MERGE_MAX], gone_id[SLAM_MERGE_MAX];
+    for (int p = 0; p < cnt; ++p) {
+        const int32_t a = pairs[2 * p], b = pairs[2 * p + 1];
+        ARG_CHECK(a >= 1 && a <= N && b >= 1 && b <= N, "landmark id out of range");
+        ARG_CHECK(a != b, "a pair names one landmark twice");
+        ARG_CHECK(!used[a] && !used[b], "a landmark appears in more than one pair (merge a chain with one call per link)");
+        used[a] = used[b] = 1;
+        gone[b] = 1;
+        keep_id[p] = a;
+        gone_id[p] = b;
+    }
+    if (Rc) {
+        ARG_CHECK(Rc[1] == Rc[2], "Rc is not symmetric");
+        ARG_CHECK(Rc[0] >= 0.0 && Rc[3] >= 0.0, "Rc has a negative diagonal");      // (a NaN fails both comparisons)
+    }
+    if (cnt == 0) {
+        if (new_index)
+            for (int j = 1; j <= N; ++j) new_index[j - 1] = j;
+        return SLAM_OK;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    int rc;
+    if ((rc = ensure_update_workspace(h, SLAM_MERGE_MAX))) return rc;
+    if ((rc = launch_merge_update(h, keep_id, gone_id, cnt, Rc))) return rc;
+    // this call's own status word; the sticky word [1] of an earlier async update stays for slam_ekf_sync
+    HIP_TRY(hipMemcpyAsync(h->h_status, h->d_status, sizeof(int32_t) * 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (h->h_status[0]) {
+        slam_set_error("merge: S is not positive definite (state left unchanged, nothing removed)");
+        return SLAM_E_NOTPD;
+    }
+    if ((rc = remove_marked(h, gone, cnt, new_index))) return rc;
+    if (new_index)
+        for (int p = 0; p < cnt; ++p) new_index[gone_id[p] - 1] = new_index[keep_id[p] - 1];
     return SLAM_OK;
 }
 

@@ -34,6 +34,7 @@ __all__ = [
     "SlamState", "EKFSlamState", "DeviceRef", "predict", "update", "add_features", "associate",
     "compute_association", "predict_observation", "mpi_to_pi", "ekf_predict_", "ekf_update_", "augment_",
     "remove_features", "remove_features_", "removal_maps",
+    "find_duplicates", "merge_features", "merge_features_", "merge_in_batches",
 ]
 
 _DTYPES = {"f32": (SLAM_F32, np.float32), "f64": (SLAM_F64, np.float64),
@@ -90,6 +91,44 @@ def removal_maps(N, ids):
     new_index = np.zeros(N, dtype=np.int32)
     new_index[left] = np.arange(1, left.size + 1, dtype=np.int32)
     return keep, new_index
+
+
+def merge_in_batches(N, pairs, merge_call, batch_max=_lib.SLAM_MERGE_MAX):
+    """Host side of EKFSlamState.merge_landmarks: any number of pairs (1-based ids of the map as it is now, N landmarks)
+    through calls of at most ``batch_max`` DISJOINT pairs each (slam_ekf_merge_landmarks takes no landmark twice in one call).
+    ``merge_call(batch)`` merges ``batch`` (int32 [m, 2], ids valid at that moment, the second of a pair leaves) and returns that
+    call's new_index; the ids of the pairs still waiting are carried through it.  A pair whose landmarks appear in no other
+    pair goes down as given (the one named second leaves, as in the C call); where pairs share a landmark (a chain a-b, b-c,
+    or the three pairs of a triple) the lowest id survives, and a pair whose landmarks have become one by then is dropped.
+    Returns new_index for the N original landmarks: the final id of the landmark each one is now part of.
+    ValueError: an id outside 1..N, or a pair that names one landmark twice."""
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    if pairs.size and (pairs.min() < 1 or pairs.max() > N):
+        raise ValueError("landmark id out of range")
+    if np.any(pairs[:, 0] == pairs[:, 1]):
+        raise ValueError("a pair names one landmark twice")
+    uses = np.bincount(pairs.reshape(-1), minlength=N + 1)
+    cur = np.arange(1, N + 1, dtype=np.int64)               # current id of the landmark that original j is part of
+    waiting = [(int(a), int(b)) for a, b in pairs]
+    while waiting:
+        batch, busy, later = [], set(), []
+        for a, b in waiting:
+            ca, cb = int(cur[a - 1]), int(cur[b - 1])
+            if ca == cb:
+                continue                                    # already one landmark
+            if len(batch) == batch_max or ca in busy or cb in busy:
+                later.append((a, b))
+                continue
+            if (uses[a] > 1 or uses[b] > 1) and cb < ca:
+                ca, cb = cb, ca                             # shared landmarks: the lowest id survives
+            batch.append((ca, cb))
+            busy.update((ca, cb))
+        if not batch:
+            break
+        new_index = np.asarray(merge_call(np.asarray(batch, dtype=np.int32)), dtype=np.int64)
+        cur = new_index[cur - 1]
+        waiting = later
+    return cur.astype(np.int32)
 
 
 def mpi_to_pi(phi):
@@ -367,6 +406,36 @@ class EKFSlamState(SlamState):
                                             _ptr(new_index, C.c_int32) if new_index.size else None))
         return new_index
 
+    def find_duplicates(self, gate, cap=1024):
+        """Pairs of landmarks that are one feature entered twice (slam_ekf_find_duplicates): (a, b), a < b, 1-based, whose
+        difference has a Mahalanobis distance below ``gate`` under the joint covariance, D = P_aa + P_bb - P_ab - P_ab'.
+        Returns ``(pairs, count)``: int32 [min(count, cap), 2] in ascending order and the number of pairs in the whole
+        map.  The state is not changed; P is read only for the pairs the means and diagonal blocks cannot rule out."""
+        cap = int(cap)
+        pairs = np.zeros((max(cap, 0), 2), dtype=np.int32)
+        count = C.c_int()
+        check(lib.slam_ekf_find_duplicates(self._h, float(gate), _ptr(pairs, C.c_int32) if cap > 0 else None, cap,
+                                           C.byref(count)))
+        return pairs[:min(count.value, max(cap, 0))], count.value
+
+    def merge_landmarks(self, pairs, Rc=None):
+        """Fuse the landmarks of every pair (1-based ids) into one, in place on the device (slam_ekf_merge_landmarks): the
+        constraint m_a - m_b = 0 with noise ``Rc`` (2 x 2, None = exact) as one Cholesky-form update per call of at most
+        SLAM_MERGE_MAX pairs, then the second landmark of each pair leaves the map as remove_landmarks removes it.  More
+        pairs, or pairs that share a landmark, are split into several calls (merge_in_batches: chains end at their lowest
+        id).  Returns ``new_index`` (int32, length N_old): the new id of old landmark j at [j - 1]; a landmark that was
+        merged away carries the new id of the one it became part of."""
+        rc = None if Rc is None else _small(Rc)
+
+        def call(batch):
+            batch = np.ascontiguousarray(batch, dtype=np.int32)
+            new_index = np.zeros(self.N, dtype=np.int32)
+            check(lib.slam_ekf_merge_landmarks(self._h, _ptr(batch, C.c_int32), int(batch.shape[0]),
+                                               _ptr(rc) if rc is not None else None, _ptr(new_index, C.c_int32)))
+            return new_index
+
+        return merge_in_batches(self.N, pairs, call)
+
     def observe(self, z, R, gate1, gate2, form="cholesky"):
         """associate -> update -> add_features (sim/ekfslam-sim.jl:114-120) in one library call with no host
         round trip between the gating and the update.  Returns the association vector
@@ -558,3 +627,18 @@ def remove_features(state: EKFSlamState, ids):
 def remove_features_(state, ids):
     """In-place name (Julia: ``remove_features!``); returns the index map as well."""
     return _state_of(state).remove_landmarks(ids)
+
+
+def find_duplicates(state: EKFSlamState, gate, cap=1024):
+    """Duplicate landmark pairs -> ``(pairs, count)`` (see EKFSlamState.find_duplicates)."""
+    return _state_of(state).find_duplicates(gate, cap)
+
+
+def merge_features(state: EKFSlamState, pairs, Rc=None):
+    """Merge the landmarks of every pair -> ``new_index`` (see EKFSlamState.merge_landmarks)."""
+    return _state_of(state).merge_landmarks(pairs, Rc)
+
+
+def merge_features_(state, pairs, Rc=None):
+    """In-place name (Julia: ``merge_landmarks!``); returns the index map as well."""
+    return _state_of(state).merge_landmarks(pairs, Rc)

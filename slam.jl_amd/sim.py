@@ -139,6 +139,7 @@ class SimLog:
     observations: list = field(default_factory=list)    # z (2 x nz) per observation step
     assoc: list = field(default_factory=list)           # (idf list, n_new) per observation step
     pruned: list = field(default_factory=list)          # (observation step, removed ids) per removal (sim(prune_after=k))
+    merged: list = field(default_factory=list)          # (observation step, pairs) per merge (sim(merge_gate=g))
     true_track: list = field(default_factory=list)
     slam_track: list = field(default_factory=list)
 
@@ -162,7 +163,7 @@ def default_QR():
 
 
 def sim(filt, waypoints: np.ndarray, landmarks: np.ndarray, seed: int, nlaps: int = 2,
-        max_steps: int = 100000, monitor=None, fused: bool = False, prune_after=None) -> SimLog:
+        max_steps: int = 100000, monitor=None, fused: bool = False, prune_after=None, merge_gate=None) -> SimLog:
     """The loop of sim/ekfslam-sim.jl:80-141 without sleep/pause.
 
     ``filt`` must already hold the initial state (x = initial pose, P = 0).
@@ -173,6 +174,10 @@ def sim(filt, waypoints: np.ndarray, landmarks: np.ndarray, seed: int, nlaps: in
     observation steps after its creation is removed with ``filt.remove_landmarks(ids) -> new_index``.  The per-landmark
     counters live here on the host (the association comes back to the host anyway) and are renumbered through
     ``new_index``; removals are recorded in ``log.pruned`` with the ids they had at that moment.
+    ``merge_gate``: None (default) changes nothing.  A number g (no counterpart in the reference): after every observation
+    step ``filt.find_duplicates(g) -> (pairs, count)`` looks for landmarks entered twice and ``filt.merge_landmarks(pairs) ->
+    new_index`` fuses them; the ``prune_after`` counters follow ``new_index`` (a merged landmark keeps the earlier birth and
+    the larger match count).  Merges are recorded in ``log.merged``.
     """
     rng = np.random.default_rng(seed)
     Q, R = default_QR()
@@ -219,6 +224,18 @@ def sim(filt, waypoints: np.ndarray, landmarks: np.ndarray, seed: int, nlaps: in
                     log.pruned.append((t, (stale + 1).tolist()))
                     left = new_index > 0
                     born, hits = born[left], hits[left]
+            if merge_gate is not None:
+                pairs, _count = filt.find_duplicates(merge_gate)
+                if len(pairs):
+                    new_index = np.asarray(filt.merge_landmarks(pairs), dtype=np.int64)
+                    log.merged.append((len(log.obs_steps) - 1, np.asarray(pairs).tolist()))
+                    if prune_after is not None:
+                        nleft = int(new_index.max()) if new_index.size else 0
+                        nborn = np.full(nleft, np.iinfo(np.int64).max, dtype=np.int64)
+                        nhits = np.zeros(nleft, dtype=np.int64)
+                        np.minimum.at(nborn, new_index - 1, born)
+                        np.maximum.at(nhits, new_index - 1, hits)
+                        born, hits = nborn, nhits
         nsteps += 1
         log.true_track.append(np.array(vehicle.pose))
         log.slam_track.append(np.array(filt.pose()))
