@@ -28,30 +28,7 @@ namespace {
 // poll: no host in the loop, no collective launch per step.
 
 
-struct PfAutoArgs {
-    void *pose0, *pose1, *logw0, *logw1;
-    const PfLmTab* lmtab;        // the landmark records' chunk table (device memory)
-    int32_t *tab0, *tab1;
-    long long n, first, n_global, seq;
-    unsigned long long seed;
-    unsigned int step;
-    int m, nl, force, lazy_ok, rank, world, publish, rec_cap;
-    double V, G, wheelbase, a0, a1, a2, dt, R00, R10, R01, R11, neff_frac;
-    double* part;
-    PfCtl* ctl;
-    int32_t* lmstate;
-    PfMirror* mir;
-    double* xchg;
-    const PfPeers* peers;        // sharded filter with peers attached (else null)
-    PfInbox* inbox;              // this rank's inbox
-    // The step's observations travel IN the kernel arguments (1.3 KB of the 4 KB a launch may carry): every one of the
-    // ~1000 workgroups reads them at its start, and from a pinned host page (the zero-copy staging of the legacy
-    // calls) that is ~5000 64-byte reads across PCIe per step -- measured: 19 us of a 46 us kernel before the first
-    // landmark record moves.  The argument segment is read through the scalar/L2 caches like any other constant.
-    double z[2 * PF_AUTO_MAXOBS];
-    int32_t ids[PF_AUTO_MAXOBS];
-};
-static_assert(sizeof(PfAutoArgs) <= 4096, "kernel argument segment");
+// (the step kernels' arguments, PfAutoArgs, and their common prologue, PfAutoStep: pf_device.h)
 
 // the first NS of six sums at once: one LDS exchange and one barrier pair for all of them (256 threads); the result reaches every thread
 template <int NS = 6>
@@ -200,13 +177,7 @@ __device__ __forceinline__ void pf_auto_tail(const PfAutoArgs& a, const int32_t*
     //      words (a grid of more than 1024 workgroups is not resident at once: a workgroup beyond the first 1024 lines
     //      may not even have started when the first pass returns). ----
     if (tid < a.m && s_first[tid]) {
-        const int32_t st = s_st[tid];
-        const int tab = st & LS_TAB, rb = (st & LS_BUF) ? 1 : 0;
-        if (tab) {
-            atomicSub(&s_tref[tab - 1], 1);
-            atomicAdd(&s_i[0], 1);                            // released its table: a landmark without one ("identity")
-        }
-        a.lmstate[s_l[tid]] = LS_SEEN | ((tab ? (rb ^ 1) : rb) ? LS_BUF : 0);
+        a.lmstate[s_l[tid]] = lm_observe(s_st[tid], s_tref, &s_i[0]);
         if (ls_pre) atomicOr(&s_obsbit[s_l[tid] >> 5], 1u << (s_l[tid] & 31));
     }
     if (xpeers) {
@@ -323,11 +294,7 @@ __device__ __forceinline__ void pf_auto_tail(const PfAutoArgs& a, const int32_t*
                 const int l = tid + 256 * j;
                 if (l < a.nl && !((s_obsbit[l >> 5] >> (l & 31)) & 1u) && (my_ls[j] & LS_TAB) == 0) a.lmstate[l] = my_ls[j] | fresh;
             }
-            if (tid < a.m && s_first[tid]) {
-                const int32_t st = s_st[tid];
-                const int tab = st & LS_TAB, rb = (st & LS_BUF) ? 1 : 0;
-                a.lmstate[s_l[tid]] = (LS_SEEN | ((tab ? (rb ^ 1) : rb) ? LS_BUF : 0)) | fresh;
-            }
+            if (tid < a.m && s_first[tid]) a.lmstate[s_l[tid]] = lm_seen_word(s_st[tid]) | fresh;
         } else {
             for (int l = tid; l < a.nl; l += 256) {
                 const int32_t st = a.lmstate[l];
@@ -379,57 +346,28 @@ __device__ __forceinline__ void pf_auto_tail(const PfAutoArgs& a, const int32_t*
 //  and a quarter of the workgroups start when the first ones end, which was measured as +10 us per step)
 template <typename T, bool PROPOSAL, bool SH>
 __global__ __launch_bounds__(256, sizeof(T) == 4 ? 4 : 2) void pf_auto_step_kernel(PfAutoArgs a) {
-    PfCtl* ctl = a.ctl;
     PF_XS(0);
     PF_WG(0);
 #if defined(SLAMHIP_EXPERIMENTS) && defined(PF_EXP_STAMPS)
     if (blockIdx.x == 0 && threadIdx.x == 0) g_xs[7] = wall_clock64();
 #endif
-    // the observed landmarks' state words are requested FIRST (their addresses need the kernel arguments only): the plan,
-    // and with it the first record requests, then waits for one round trip (control block and state words together), not two
-    typedef const __attribute__((address_space(4))) PfAutoArgs* KargPtr0;
-    const KargPtr0 ka0 = (KargPtr0)__builtin_amdgcn_kernarg_segment_ptr();
-    int l_pre = 0;
-    int32_t st_pre = 0;
-    if ((int)threadIdx.x < a.m) {
-        l_pre = ka0->ids[threadIdx.x] - 1;
-        st_pre = a.lmstate[l_pre];
-    }
-    // the control words this step needs, in one go (one cache line, one round trip)
-    const long long halted = ctl->halt_seq;
-    const int pcur = ctl->pcur, tside = ctl->tside, lwcur = ctl->lwcur;
-    const double shift_next = ctl->shift_next;
-    if (halted != 0 || ctl->error != 0) return;        // an earlier step waits for the host (which replays this one), or failed
-    if constexpr (SH) {
-        // a peer is destroying its handle: touch none of its memory (sweep_load, the inbox writes); the filter is dead
-        if (pf_peer_gone(a.inbox, a.world)) {
-            if (blockIdx.x == 0 && threadIdx.x == 0) {
-                ctl->error = PF_ERR_PEER;
-                pf_publish(a.mir, 0.0, (long long)ctl->nresamples, ctl->resample_seq, PF_ERR_PEER, a.seq, a.seq);
-            }
-            return;
-        }
-    }
+    PfAutoStep<T, SH> s;
+    int32_t st_pre;                                    // (declared in this order: the other one moves them to other registers)
+    int l_pre;
+    if (!s.begin(a, l_pre, st_pre)) return;
     PF_XS(1);
-    if (blockIdx.x == 0 && threadIdx.x == 0) ctl->stamps[0] = wall_clock64();
-    __shared__ T s_obs[2 * PF_AUTO_MAXOBS];          // the observations in the state dtype: converted once per workgroup
+    __shared__ T s_obs[2 * PF_AUTO_MAXOBS];
     __shared__ int32_t s_ids[PF_AUTO_MAXOBS], s_meta[PF_AUTO_MAXOBS], s_l[PF_AUTO_MAXOBS], s_st[PF_AUTO_MAXOBS], s_first[PF_AUTO_MAXOBS];
+    s.started(a);
     const int m = a.m;
-    // the observations: read from the argument segment itself (constant address space, dynamic index) -- going through
-    // the by-value copy `a` would put the whole 1.3 KB struct into scratch memory
-    typedef const __attribute__((address_space(4))) PfAutoArgs* KargPtr;
-    const KargPtr ka = (KargPtr)__builtin_amdgcn_kernarg_segment_ptr();
-    for (int i = threadIdx.x; i < 2 * m; i += blockDim.x) s_obs[i] = (T)ka->z[i];
-    const T pend = (T)shift_next;
-    T* pose = (T*)(pcur ? a.pose1 : a.pose0);
-    T* logw = (T*)(lwcur ? a.logw1 : a.logw0);
-    const int32_t* tabs = tside ? a.tab1 : a.tab0;
+    for (int i = threadIdx.x; i < 2 * m; i += blockDim.x) s_obs[i] = (T)s.ka->z[i];      // converted once per workgroup
+    s.sides(a);
+    T* const pose = s.pose;
+    T* const logw = s.logw;
     const int64_t n = a.n;
     const int64_t pi = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const bool valid = pi < n;
     const int64_t p = valid ? pi : n - 1;              // idle lanes shadow the last particle, stores are masked
-    PfShardCtx sc{};
-    if constexpr (SH) sc = PfShardCtx{a.peers, (uint32_t)a.first, (uint32_t)a.n, a.rank, a.world};
     // the particle's pose and weight are requested, and its noise drawn, BEFORE the plan's two barriers and its dependent
     // loads (ids -> state words): the motion model then starts as soon as the plan stands
     T x = 0, y = 0, phi = 0, lw = 0, e1 = 0, e2 = 0;
@@ -441,13 +379,13 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? 4 : 2) void pf_auto_step_kern
     plan_obs(l_pre, st_pre, m, s_l, s_st, s_ids, s_meta, s_first);
     PF_XS(2);
     if (PROPOSAL)
-        proposal_core<T, SH>(pose, LmView<T>{a.lmtab}, tabs, logw, n, a.first, a.step, a.seed, (T)a.V, (T)a.G, (T)a.wheelbase, (T)a.a0,
-                             (T)a.a1, (T)a.a2, (T)a.dt, s_obs, s_ids, s_meta, m, (T)a.R00, (T)a.R10, (T)a.R01, (T)a.R11, pend, p, valid, x,
-                             y, phi, lw, sc);
+        proposal_core<T, SH>(pose, LmView<T>{a.lmtab}, s.tabs, logw, n, a.first, a.step, a.seed, (T)a.V, (T)a.G, (T)a.wheelbase,
+                             (T)a.a0, (T)a.a1, (T)a.a2, (T)a.dt, s_obs, s_ids, s_meta, m, (T)a.R00, (T)a.R10, (T)a.R01,
+                             (T)a.R11, s.pend, p, valid, x, y, phi, lw, s.sc);
     else
-        step_core<T, true, true, SH>(pose, LmView<T>{a.lmtab}, tabs, logw, n, a.first, a.step, a.seed, (T)a.V, (T)a.G,
-                                     (T)a.wheelbase, (T)a.a0, (T)a.a1, (T)a.dt, s_obs, s_ids, s_meta, m, (T)a.R00, (T)a.R10, (T)a.R01,
-                                     (T)a.R11, pend, p, valid, x, y, phi, lw, e1, e2, sc);
+        step_core<T, true, true, SH>(pose, LmView<T>{a.lmtab}, s.tabs, logw, n, a.first, a.step, a.seed, (T)a.V, (T)a.G,
+                                     (T)a.wheelbase, (T)a.a0, (T)a.a1, (T)a.dt, s_obs, s_ids, s_meta, m, (T)a.R00,
+                                     (T)a.R10, (T)a.R01, (T)a.R11, s.pend, p, valid, x, y, phi, lw, e1, e2, s.sc);
     PF_XS(4);
     PF_WG(1);
     wrec_block_line<T>(lw, valid, a.part, a.seq);          // the tree's 256-particle node as a tagged line, not waited for
@@ -456,7 +394,7 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? 4 : 2) void pf_auto_step_kern
     // the workgroup with the highest index collects the lines.  The wait cannot deadlock because NO other workgroup waits
     // for anything: each runs to its end on its own, whenever the dispatcher starts it (the dispatch order is not relied
     // on), and the collection ends on a time-out
-    if (blockIdx.x == gridDim.x - 1) pf_auto_tail<T>(a, s_l, s_st, s_first, pcur, tside, lwcur, 1);
+    if (blockIdx.x == gridDim.x - 1) pf_auto_tail<T>(a, s_l, s_st, s_first, s.pcur, s.tside, s.lwcur, 1);
 }
 
 // ---- the same step with the OBSERVATIONS in parallel (small filters / shards) -----------------------------------------
@@ -473,65 +411,35 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? 4 : 2) void pf_auto_step_kern
 
 template <typename T, bool SH>
 __global__ __launch_bounds__(64 * PAR_WAVES) void pf_auto_step_par_kernel(PfAutoArgs a) {
-    PfCtl* ctl = a.ctl;
-    typedef const __attribute__((address_space(4))) PfAutoArgs* KargPtr;
-    const KargPtr ka = (KargPtr)__builtin_amdgcn_kernarg_segment_ptr();
-    int l_pre = 0;
-    int32_t st_pre = 0;
-    if ((int)threadIdx.x < a.m) {
-        l_pre = ka->ids[threadIdx.x] - 1;
-        st_pre = a.lmstate[l_pre];
-    }
-    const long long halted = ctl->halt_seq;
-    const int pcur = ctl->pcur, tside = ctl->tside, lwcur = ctl->lwcur;
-    const double shift_next = ctl->shift_next;
-    if (halted != 0 || ctl->error != 0) return;
-    if constexpr (SH) {
-        if (pf_peer_gone(a.inbox, a.world)) {              // (see pf_auto_step_kernel)
-            if (blockIdx.x == 0 && threadIdx.x == 0) {
-                ctl->error = PF_ERR_PEER;
-                pf_publish(a.mir, 0.0, (long long)ctl->nresamples, ctl->resample_seq, PF_ERR_PEER, a.seq, a.seq);
-            }
-            return;
-        }
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) ctl->stamps[0] = wall_clock64();
+    PfAutoStep<T, SH> s;
+    int l_pre;
+    int32_t st_pre;
+    if (!s.begin(a, l_pre, st_pre)) return;
     __shared__ T s_obs[2 * PF_AUTO_MAXOBS];
     __shared__ int32_t s_ids[PF_AUTO_MAXOBS], s_meta[PF_AUTO_MAXOBS], s_l[PF_AUTO_MAXOBS], s_st[PF_AUTO_MAXOBS], s_first[PF_AUTO_MAXOBS];
     __shared__ T s_pose[3][64];
     __shared__ T s_term[PF_AUTO_MAXOBS][64];
+    s.started(a);
     const int m = a.m;
-    for (int i = threadIdx.x; i < 2 * m; i += blockDim.x) s_obs[i] = (T)ka->z[i];
-    const T pend = (T)shift_next;
-    T* pose = (T*)(pcur ? a.pose1 : a.pose0);
-    T* logw = (T*)(lwcur ? a.logw1 : a.logw0);
-    const int32_t* tabs = tside ? a.tab1 : a.tab0;
+    for (int i = threadIdx.x; i < 2 * m; i += blockDim.x) s_obs[i] = (T)s.ka->z[i];      // converted once per workgroup
+    s.sides(a);
+    T* const pose = s.pose;
     const int64_t n = a.n;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
     const int64_t pi = (int64_t)blockIdx.x * 64 + lane;
     const bool valid = pi < n;
     const int64_t p = valid ? pi : n - 1;
-    PfShardCtx sc{};
-    if constexpr (SH) sc = PfShardCtx{a.peers, (uint32_t)a.first, (uint32_t)a.n, a.rank, a.world};
     T x = 0, y = 0, phi = 0, lw = 0;
     if (wave == 0) {                                     // F1: the motion model, once per particle
         x = pose[p]; y = pose[n + p]; phi = pose[2 * n + p];
-        lw = logw[p];
+        lw = s.logw[p];
         T e1, e2;
         normals2<T>((uint64_t)(a.first + p), a.step, STREAM_PREDICT, a.seed, e1, e2);
-        const T Vn = (T)a.V + (T)a.a0 * e1;              // sim/sim-utils.jl:36
-        const T Gn = (T)a.G + (T)a.a1 * e2;              // :37
-        T sgp, cgp, sg, cg;
-        m_sincos<T>(Gn + phi, sgp, cgp);
-        m_sincos<T>(Gn, sg, cg);
-        const T xn = x + Vn * (T)a.dt * cgp;             // src/ekf.jl:39-41
-        const T yn = y + Vn * (T)a.dt * sgp;
-        const T pn = wrap_pi<T>(phi + Vn * (T)a.dt * sg / (T)a.wheelbase);
-        x = xn; y = yn; phi = pn;
-        if (valid) { pose[p] = x; pose[n + p] = y; pose[2 * n + p] = phi; }
+        const PfPose<T> q = motion_noisy<T, double>(a.V, a.G, a.a0, a.a1, e1, e2, a.dt, a.wheelbase, x, y, phi, valid, pose, n, p);
+        x = q.x; y = q.y; phi = q.phi;
         s_pose[0][lane] = x; s_pose[1][lane] = y; s_pose[2][lane] = phi;
     }
-    plan_obs(l_pre, st_pre, m, s_l, s_st, s_ids, s_meta, s_first);       // (two barriers: the pose is in LDS behind them)
+    plan_obs(l_pre, st_pre, m, s_l, s_st, s_ids, s_meta, s_first);    // (two barriers: the pose is in LDS behind them)
     if (wave != 0) { x = s_pose[0][lane]; y = s_pose[1][lane]; phi = s_pose[2][lane]; }
     const T R00 = (T)a.R00, R10 = (T)a.R10, R01 = (T)a.R01, R11 = (T)a.R11;
     const LmView<T> lv{a.lmtab};
@@ -545,17 +453,17 @@ __global__ __launch_bounds__(64 * PAR_WAVES) void pf_auto_step_par_kernel(PfAuto
         if (code & NEW_FLAG) {
             lm_init<T>(row, n, x, y, phi, r, b, R00, R10, R01, R11, valid);
         } else {
-            const LmRow<T> cur = sweep_load<T, 2, SH>(lv, tabs, n, (uint32_t)p, code, meta, sc);
+            const LmRow<T> cur = sweep_load<T, 2, SH>(lv, s.tabs, n, (uint32_t)p, code, meta, s.sc);
             lm_update<T>(row, n, cur, x, y, phi, r, b, R00, R10, R01, R11, valid, term);      // term = 0 + (this observation's log-weight term)
         }
         s_term[i][lane] = term;
     }
     __syncthreads();
     if (wave == 0) {
-        lw -= pend;
+        lw -= s.pend;
         for (int i = 0; i < m; ++i)
             if (!(__builtin_amdgcn_readfirstlane(s_ids[i]) & NEW_FLAG)) lw += s_term[i][lane];     // observation order
-        if (valid) logw[p] = lw;
+        if (valid) s.logw[p] = lw;
     }
     if (wave == 0) {                                       // the tree's leaf (this workgroup's 64 particles) as a tagged line
         const WRec leaf = wrec_wave<T>(lw, valid);
@@ -563,7 +471,7 @@ __global__ __launch_bounds__(64 * PAR_WAVES) void pf_auto_step_par_kernel(PfAuto
     }
     if (blockIdx.x == gridDim.x - 1) {
         if (threadIdx.x >= 256) return;                  // the tail is written for four waves
-        pf_auto_tail<T>(a, s_l, s_st, s_first, pcur, tside, lwcur, 0);
+        pf_auto_tail<T>(a, s_l, s_st, s_first, s.pcur, s.tside, s.lwcur, 0);
     }
 }
 
@@ -582,39 +490,19 @@ template <typename T>
 constexpr int WAY_MAXOBS = sizeof(T) == 4 ? 32 : 16;     // the term array [m][256] stays within 32 KB of LDS
 template <typename T, bool SH, int W>
 __global__ __launch_bounds__(256 * W) void pf_auto_step_way_kernel(PfAutoArgs a) {
-    PfCtl* ctl = a.ctl;
-    typedef const __attribute__((address_space(4))) PfAutoArgs* KargPtr;
-    const KargPtr ka = (KargPtr)__builtin_amdgcn_kernarg_segment_ptr();
-    int l_pre = 0;
-    int32_t st_pre = 0;
-    if ((int)threadIdx.x < a.m) {
-        l_pre = ka->ids[threadIdx.x] - 1;
-        st_pre = a.lmstate[l_pre];
-    }
-    const long long halted = ctl->halt_seq;
-    const int pcur = ctl->pcur, tside = ctl->tside, lwcur = ctl->lwcur;
-    const double shift_next = ctl->shift_next;
-    if (halted != 0 || ctl->error != 0) return;
-    if constexpr (SH) {
-        if (pf_peer_gone(a.inbox, a.world)) {              // (see pf_auto_step_kernel)
-            if (blockIdx.x == 0 && threadIdx.x == 0) {
-                ctl->error = PF_ERR_PEER;
-                pf_publish(a.mir, 0.0, (long long)ctl->nresamples, ctl->resample_seq, PF_ERR_PEER, a.seq, a.seq);
-            }
-            return;
-        }
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) ctl->stamps[0] = wall_clock64();
+    PfAutoStep<T, SH> s;
+    int l_pre;
+    int32_t st_pre;
+    if (!s.begin(a, l_pre, st_pre)) return;
     __shared__ T s_obs[2 * PF_AUTO_MAXOBS];
     __shared__ int32_t s_ids[PF_AUTO_MAXOBS], s_meta[PF_AUTO_MAXOBS], s_l[PF_AUTO_MAXOBS], s_st[PF_AUTO_MAXOBS], s_first[PF_AUTO_MAXOBS];
     __shared__ T s_pose[3][256];
     __shared__ T s_term[WAY_MAXOBS<T>][256];
+    s.started(a);
     const int m = a.m;
-    for (int i = threadIdx.x; i < 2 * m; i += blockDim.x) s_obs[i] = (T)ka->z[i];
-    const T pend = (T)shift_next;
-    T* pose = (T*)(pcur ? a.pose1 : a.pose0);
-    T* logw = (T*)(lwcur ? a.logw1 : a.logw0);
-    const int32_t* tabs = tside ? a.tab1 : a.tab0;
+    for (int i = threadIdx.x; i < 2 * m; i += blockDim.x) s_obs[i] = (T)s.ka->z[i];      // converted once per workgroup
+    s.sides(a);
+    T* const pose = s.pose;
     const int64_t n = a.n;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
     const int way = wave >> 2;                               // 0 .. W-1 (wave-uniform)
@@ -622,27 +510,17 @@ __global__ __launch_bounds__(256 * W) void pf_auto_step_way_kernel(PfAutoArgs a)
     const int64_t pi = (int64_t)blockIdx.x * 256 + pl;
     const bool valid = pi < n;
     const int64_t p = valid ? pi : n - 1;
-    PfShardCtx sc{};
-    if constexpr (SH) sc = PfShardCtx{a.peers, (uint32_t)a.first, (uint32_t)a.n, a.rank, a.world};
     T x = 0, y = 0, phi = 0, lw = 0;
     if (way == 0) {                                          // F1: the motion model, once per particle
         x = pose[p]; y = pose[n + p]; phi = pose[2 * n + p];
-        lw = logw[p];
+        lw = s.logw[p];
         T e1, e2;
         normals2<T>((uint64_t)(a.first + p), a.step, STREAM_PREDICT, a.seed, e1, e2);
-        const T Vn = (T)a.V + (T)a.a0 * e1;                  // sim/sim-utils.jl:36
-        const T Gn = (T)a.G + (T)a.a1 * e2;                  // :37
-        T sgp, cgp, sg, cg;
-        m_sincos<T>(Gn + phi, sgp, cgp);
-        m_sincos<T>(Gn, sg, cg);
-        const T xn = x + Vn * (T)a.dt * cgp;                 // src/ekf.jl:39-41
-        const T yn = y + Vn * (T)a.dt * sgp;
-        const T pn = wrap_pi<T>(phi + Vn * (T)a.dt * sg / (T)a.wheelbase);
-        x = xn; y = yn; phi = pn;
-        if (valid) { pose[p] = x; pose[n + p] = y; pose[2 * n + p] = phi; }
+        const PfPose<T> q = motion_noisy<T, double>(a.V, a.G, a.a0, a.a1, e1, e2, a.dt, a.wheelbase, x, y, phi, valid, pose, n, p);
+        x = q.x; y = q.y; phi = q.phi;
         s_pose[0][pl] = x; s_pose[1][pl] = y; s_pose[2][pl] = phi;
     }
-    plan_obs(l_pre, st_pre, m, s_l, s_st, s_ids, s_meta, s_first);       // (two barriers: the pose is in LDS behind them)
+    plan_obs(l_pre, st_pre, m, s_l, s_st, s_ids, s_meta, s_first);    // (two barriers: the pose is in LDS behind them)
     if (way != 0) { x = s_pose[0][pl]; y = s_pose[1][pl]; phi = s_pose[2][pl]; }
     const T R00 = (T)a.R00, R10 = (T)a.R10, R01 = (T)a.R01, R11 = (T)a.R11;
     const LmView<T> lv{a.lmtab};
@@ -658,7 +536,7 @@ __global__ __launch_bounds__(256 * W) void pf_auto_step_way_kernel(PfAutoArgs a)
         ring[u] = LmRow<T>{0, 0, 0, 0, 0};
         const int i = way + W * u;
         if (u < cnt && !(uni(s_ids[i]) & NEW_FLAG)) {
-            ring[u] = sweep_load<T, 2, SH>(lv, tabs, n, (uint32_t)p, uni(s_ids[i]), uni(s_meta[i]), sc);
+            ring[u] = sweep_load<T, 2, SH>(lv, s.tabs, n, (uint32_t)p, uni(s_ids[i]), uni(s_meta[i]), s.sc);
             have[u] = true;
         }
     }
@@ -680,7 +558,7 @@ __global__ __launch_bounds__(256 * W) void pf_auto_step_way_kernel(PfAutoArgs a)
             if (jn < cnt) {
                 const int in = way + W * jn;
                 if (!(uni(s_ids[in]) & NEW_FLAG)) {
-                    ring[u] = sweep_load<T, 2, SH>(lv, tabs, n, (uint32_t)p, uni(s_ids[in]), uni(s_meta[in]), sc);
+                    ring[u] = sweep_load<T, 2, SH>(lv, s.tabs, n, (uint32_t)p, uni(s_ids[in]), uni(s_meta[in]), s.sc);
                     have[u] = true;
                 }
             }
@@ -688,7 +566,7 @@ __global__ __launch_bounds__(256 * W) void pf_auto_step_way_kernel(PfAutoArgs a)
             if (code & NEW_FLAG) {                           // F3: first sighting
                 lm_init<T>(row, n, x, y, phi, r, b, R00, R10, R01, R11, valid);
             } else {
-                if (!have_cur) cur = sweep_load<T, 2, SH>(lv, tabs, n, (uint32_t)p, code, meta, sc);
+                if (!have_cur) cur = sweep_load<T, 2, SH>(lv, s.tabs, n, (uint32_t)p, code, meta, s.sc);
                 lm_update<T>(row, n, cur, x, y, phi, r, b, R00, R10, R01, R11, valid, term);      // term = 0 + (this observation's log-weight term)
             }
             s_term[i][pl] = term;
@@ -696,15 +574,15 @@ __global__ __launch_bounds__(256 * W) void pf_auto_step_way_kernel(PfAutoArgs a)
     }
     __syncthreads();
     if (way == 0) {
-        lw -= pend;
+        lw -= s.pend;
         for (int i = 0; i < m; ++i)
             if (!(uni(s_ids[i]) & NEW_FLAG)) lw += s_term[i][pl];                                 // observation order
-        if (valid) logw[p] = lw;
+        if (valid) s.logw[p] = lw;
     }
     wrec_block_line<T>(lw, valid, a.part, a.seq);            // (the first four waves = way 0 hold the 256 weights)
     if (blockIdx.x == gridDim.x - 1) {
         if (threadIdx.x >= 256) return;                      // the tail is written for four waves
-        pf_auto_tail<T>(a, s_l, s_st, s_first, pcur, tside, lwcur, 1);
+        pf_auto_tail<T>(a, s_l, s_st, s_first, s.pcur, s.tside, s.lwcur, 1);
     }
 }
 
@@ -722,8 +600,7 @@ __global__ __launch_bounds__(256 * W) void pf_auto_step_way_kernel(PfAutoArgs a)
 //             MAPS do not move: a table entry is a global particle id and the sweep reads a remote ancestor's record
 //             from its owner when the landmark is next updated (sweep_load<SH>).  Uniform weights go to the OTHER
 //             log-weight buffer, poses and tables to their other sides: a peer that is still reading this rank's
-//             step-s state reads buffers nobody writes.  Why no further hand-shake is needed: a rank writes those old
-//             sides again at its resampling s' > s at the earliest, which needs every rank's scalars of step s', which
+//             step-s state reads buffers nobody writes.
 
 
 // The cdf of the step that resamples (pf_scan1_kernel behind the control block's gate), over the weights of the WHOLE

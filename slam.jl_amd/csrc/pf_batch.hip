@@ -245,7 +245,7 @@ __global__ __launch_bounds__(PB_THREADS) void pf_batch_kernel(PbArgs a) {
         step_hdr(t, V, G, off, m);
         const long long seq = a.seq0 + t;
         PB_TR(0);
-        // ---- the step's observations and their plan (pf_auto.hip: plan_obs), from the replayed state words ----
+        // ---- the step's observations and their plan (pf_device.h: plan_obs), from the replayed state words ----
         if (tid < 2 * m) s_obs[tid] = __uint_as_float(ka->blob[off + 3 * (tid >> 1) + (tid & 1)]);
         int l_pre = 0;
         int32_t st_pre = 0;
@@ -253,7 +253,7 @@ __global__ __launch_bounds__(PB_THREADS) void pf_batch_kernel(PbArgs a) {
             l_pre = (int)ka->blob[off + 3 * tid + 2] - 1;
             st_pre = s_lm[l_pre];
         }
-        // F1, the motion model (sim/sim-utils.jl:36-37, src/ekf.jl:39-41): once per particle, by way 0
+        // F1, the motion model (pf_device.h: motion_noisy, written out -- see there): once per particle, by way 0
         auto motion = [&]() __attribute__((always_inline)) {
             T e1, e2;
             normals2<T>((uint64_t)(a.first + p), a.step0 + (unsigned)t, STREAM_PREDICT, a.seed, e1, e2);
@@ -276,15 +276,7 @@ __global__ __launch_bounds__(PB_THREADS) void pf_batch_kernel(PbArgs a) {
         }
         plan_obs(l_pre, st_pre, m, s_l, s_st, s_ids, s_meta, s_first);        // (two barriers: the pose is in LDS behind them)
         // this step's state transitions (pf_auto_tail does them in the control block; here in every workgroup's copy)
-        if (tid < m && s_first[tid]) {
-            const int32_t st = s_st[tid];
-            const int tab = st & LS_TAB, rb = (st & LS_BUF) ? 1 : 0;
-            if (tab) {
-                atomicSub(&s_tref[tab - 1], 1);
-                atomicAdd(&s_i[0], 1);                            // released its table: a landmark without one ("identity")
-            }
-            s_lm[s_l[tid]] = LS_SEEN | ((tab ? (rb ^ 1) : rb) ? LS_BUF : 0);
-        }
+        if (tid < m && s_first[tid]) s_lm[s_l[tid]] = lm_observe(s_st[tid], s_tref, &s_i[0]);
         if constexpr (W > 1) {
             if (way != 0) { x = s_pose[0][pl]; y = s_pose[1][pl]; phi = s_pose[2][pl]; }
         }

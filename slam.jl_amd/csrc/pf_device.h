@@ -1,6 +1,7 @@
 // pf_device.h -- device code shared by the particle path's kernels (included inside each translation unit's anonymous
-// namespace): Philox, the fp32 arithmetic of the sweep, the 2 x 2 landmark EKF, the record ring of the sweep, the step cores,
-// the weight statistics (legacy block partials and the canonical tree of the auto mode).
+// namespace): Philox, the fp32 arithmetic of the sweep, the 2 x 2 landmark EKF, the record ring of the sweep, the motion model,
+// the step cores, the weight statistics (legacy block partials and the canonical tree of the auto mode), the auto mode's step
+// plan, bookkeeping and prologue.
 #pragma once
 #include "pf_internal.h"
 
@@ -646,6 +647,34 @@ __device__ __forceinline__ void apply_known(const LmView<T> lv, const int32_t* _
     k.run(lv, tabs, n, (uint32_t)p, s_obs, s_ids, s_meta, m, x, y, phi, R00, R10, R01, R11, valid, lw, sc);
 }
 
+// F1, the motion model: the pose under the control (Vn, Gn) as this particle sees it, stored if the lane holds a particle.
+// Every step kernel must move a particle to the same bits.  The pose goes in and comes back by value, and dt / wheelbase
+// are converted to the state dtype (C: double in the kernel arguments) where they are used: in this shape the helper
+// compiles to the instructions of the code written out.  step_core below, pf_batch_kernel (on its 128-register ceiling) and
+// pf_predict_kernel (stores each coordinate as it is formed) keep it written out: a change here is a change there.
+template <typename T>
+struct PfPose { T x, y, phi; };
+template <typename T, typename C>
+__device__ __forceinline__ PfPose<T> motion_pose(T Vn, T Gn, C dt, C wheelbase, T x, T y, T phi, bool valid, T* pose, int64_t n,
+                                                 int64_t p) {
+    T sgp, cgp, sg, cg;
+    m_sincos<T>(Gn + phi, sgp, cgp);
+    m_sincos<T>(Gn, sg, cg);
+    const T xn = x + Vn * (T)dt * cgp;                // src/ekf.jl:39-41
+    const T yn = y + Vn * (T)dt * sgp;
+    const T pn = wrap_pi<T>(phi + Vn * (T)dt * sg / (T)wheelbase);
+    if (valid) { pose[p] = xn; pose[n + p] = yn; pose[2 * n + p] = pn; }
+    return PfPose<T>{xn, yn, pn};
+}
+// ... under the control (V, G) with the particle's own noise: e1, e2 its two normal deviates
+template <typename T, typename C>
+__device__ __forceinline__ PfPose<T> motion_noisy(C V, C G, C sigV, C sigG, T e1, T e2, C dt, C wheelbase, T x, T y, T phi,
+                                                  bool valid, T* pose, int64_t n, int64_t p) {
+    const T Vn = (T)V + (T)sigV * e1;                 // sim/sim-utils.jl:36
+    const T Gn = (T)G + (T)sigG * e2;                 // :37
+    return motion_pose<T, C>(Vn, Gn, dt, wheelbase, x, y, phi, valid, pose, n, p);
+}
+
 // One particle's filter step: predict (PREDICT), the m known-id updates, the log-weight.  Shared by the legacy kernels
 // (observation codes staged by the host) and the auto mode's kernel (codes planned on the device).
 // PRELOADED (the auto mode's kernel): x, y, phi hold the particle's pose, lw its stored log-weight and e1, e2 its two
@@ -669,6 +698,7 @@ __device__ __forceinline__ void step_core(T* __restrict__ pose, const LmView<T> 
 #else
         if (!PRELOADED) normals2<T>((uint64_t)(first + p), step, STREAM_PREDICT, seed, e1, e2);
 #endif
+        // (motion_noisy written out: through the helper the double-precision kernels' instructions move)
         const T Vn = V + sigV * e1;                       // sim/sim-utils.jl:36
         const T Gn = G + sigG * e2;                       // :37
         T sgp, cgp, sg, cg;
@@ -794,13 +824,9 @@ __device__ __forceinline__ void proposal_core(T* __restrict__ pose, const LmView
     const T w1 = mu1 + l10 * e1 + l11 * e2;
     const T Vn = V + lq00 * w0;
     const T Gn = G + (lq10 * w0 + lq11 * w1);
-    T sgp, cgp, sgn, cgn;
-    m_sincos<T>(Gn + phi, sgp, cgp);
-    m_sincos<T>(Gn, sgn, cgn);
-    const T xn = x + Vn * dt * cgp;                   // src/ekf.jl:39-41
-    const T yn = y + Vn * dt * sgp;
-    const T pn = wrap_pi<T>(phi + Vn * dt * sgn / wheelbase);
-    if (valid) { pose[p] = xn; pose[n + p] = yn; pose[2 * n + p] = pn; logw[p] = lw; }
+    const PfPose<T> q = motion_pose<T, T>(Vn, Gn, dt, wheelbase, x, y, phi, valid, pose, n, p);
+    const T xn = q.x, yn = q.y, pn = q.phi;
+    if (valid) logw[p] = lw;
     T unused = 0;
     apply_known<T, SH>(lv, tabs, n, p, s_obs, s_ids, s_meta, m, xn, yn, pn, R00, R10, R01, R11, valid, unused, sc);
     xo = xn; yo = yn; po = pn; lwo = lw;
@@ -952,6 +978,21 @@ __device__ __forceinline__ void plan_obs(int l_mine, int32_t st_mine, int m, int
     __syncthreads();
 }
 
+// The state word an observed landmark is left with (what pf_stage does on the host): seen, in the buffer the update wrote.
+__device__ __forceinline__ int32_t lm_seen_word(int32_t st) {
+    const int tab = st & LS_TAB, rb = (st & LS_BUF) ? 1 : 0;
+    return LS_SEEN | ((tab ? (rb ^ 1) : rb) ? LS_BUF : 0);
+}
+// ... and the transition, by the thread of the landmark's first observation: a table is released (s_tref: reference counts, LDS)
+__device__ __forceinline__ int32_t lm_observe(int32_t st, int* s_tref, int* s_identity) {
+    const int tab = st & LS_TAB, rb = (st & LS_BUF) ? 1 : 0;
+    if (tab) {
+        atomicSub(&s_tref[tab - 1], 1);
+        atomicAdd(s_identity, 1);
+    }
+    return LS_SEEN | ((tab ? (rb ^ 1) : rb) ? LS_BUF : 0);             // (= lm_seen_word(st))
+}
+
 // One lane writes a step's outcome to the host's mirror (pinned memory).
 __device__ __forceinline__ void pf_publish(PfMirror* mir, double neff, long long nresamples, long long resampled_seq, int error,
                                            long long halt_seq, long long seq) {
@@ -967,5 +1008,89 @@ __device__ __forceinline__ void pf_publish(PfMirror* mir, double neff, long long
     __hip_atomic_store(&mir->done_seq, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+
+// ---- the auto mode's step kernels (pf_auto.hip): their arguments and the prologue they share ------------------------------
+struct PfAutoArgs {
+    void *pose0, *pose1, *logw0, *logw1;
+    const PfLmTab* lmtab;        // the landmark records' chunk table (device memory)
+    int32_t *tab0, *tab1;
+    long long n, first, n_global, seq;
+    unsigned long long seed;
+    unsigned int step;
+    int m, nl, force, lazy_ok, rank, world, publish, rec_cap;
+    double V, G, wheelbase, a0, a1, a2, dt, R00, R10, R01, R11, neff_frac;
+    double* part;
+    PfCtl* ctl;
+    int32_t* lmstate;
+    PfMirror* mir;
+    double* xchg;
+    const PfPeers* peers;        // sharded filter with peers attached (else null)
+    PfInbox* inbox;              // this rank's inbox
+    // The step's observations travel IN the kernel arguments (1.3 KB of the 4 KB a launch may carry): every one of the
+    // ~1000 workgroups reads them at its start, and from a pinned host page (the zero-copy staging of the legacy
+    // calls) that is ~5000 64-byte reads across PCIe per step -- measured: 19 us of a 46 us kernel before the first
+    // landmark record moves.  The argument segment is read through the scalar/L2 caches like any other constant.
+    double z[2 * PF_AUTO_MAXOBS];
+    int32_t ids[PF_AUTO_MAXOBS];
+};
+static_assert(sizeof(PfAutoArgs) <= 4096, "kernel argument segment");
+
+// What every auto-step kernel does before its particles: begin(), started(), the kernel's own loop that stages the
+// observations from ka->z into LDS, then sides().  In pieces because the sequential kernel stamps the time between the
+// first two, and because the staging loop written in the kernel, between the start stamp and the sides, is what keeps the
+// three kernels' instructions those of the prologue written out.  The order of the pieces is the load-latency-critical one.
+template <typename T, bool SH>
+struct PfAutoStep {
+    // the argument segment itself: the observations are read through it (through `a`, the 1.3 KB struct would go to scratch)
+    const __attribute__((address_space(4))) PfAutoArgs* ka;
+    int pcur, tside, lwcur;             // the live sides of pose / tables / log-weights (pf_auto_tail flips them)
+    double shift_next;
+    T pend;                             // the normalisation shift the previous step deferred (shift_next in the state dtype)
+    T* pose;                            // the live buffers
+    T* logw;
+    const int32_t* tabs;
+    PfShardCtx sc;
+    // false: this step does not run (the same answer in every thread).  l_pre, st_pre: thread i < m gets observation i's
+    // landmark and its state word, for plan_obs (the kernel's locals: as members they come out in other registers)
+    __device__ __forceinline__ bool begin(const PfAutoArgs& a, int& l_pre, int32_t& st_pre) {
+        PfCtl* ctl = a.ctl;
+        // the observed landmarks' state words are requested FIRST (their addresses need the kernel arguments only): the plan,
+        // and with it the first record requests, then waits for one round trip (control block and state words together), not two
+        ka = (const __attribute__((address_space(4))) PfAutoArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+        l_pre = 0; st_pre = 0;
+        if ((int)threadIdx.x < a.m) {
+            l_pre = ka->ids[threadIdx.x] - 1;
+            st_pre = a.lmstate[l_pre];
+        }
+        // the control words this step needs, in one go (one cache line, one round trip)
+        const long long halted = ctl->halt_seq;
+        pcur = ctl->pcur; tside = ctl->tside; lwcur = ctl->lwcur;
+        shift_next = ctl->shift_next;
+        if (halted != 0 || ctl->error != 0) return false;  // an earlier step waits for the host (which replays this one), or failed
+        if constexpr (SH) {
+            // a peer is destroying its handle: touch none of its memory (sweep_load, the inbox writes); the filter is dead
+            if (pf_peer_gone(a.inbox, a.world)) {
+                if (blockIdx.x == 0 && threadIdx.x == 0) {
+                    ctl->error = PF_ERR_PEER;
+                    pf_publish(a.mir, 0.0, (long long)ctl->nresamples, ctl->resample_seq, PF_ERR_PEER, a.seq, a.seq);
+                }
+                return false;
+            }
+        }
+        return true;
+    }
+    __device__ __forceinline__ void started(const PfAutoArgs& a) {       // the step's start stamp
+        if (blockIdx.x == 0 && threadIdx.x == 0) a.ctl->stamps[0] = wall_clock64();
+    }
+    // the live sides, from the control words begin() read
+    __device__ __forceinline__ void sides(const PfAutoArgs& a) {
+        pend = (T)shift_next;
+        pose = (T*)(pcur ? a.pose1 : a.pose0);
+        logw = (T*)(lwcur ? a.logw1 : a.logw0);
+        tabs = tside ? a.tab1 : a.tab0;
+        sc = PfShardCtx{};
+        if constexpr (SH) sc = PfShardCtx{a.peers, (uint32_t)a.first, (uint32_t)a.n, a.rank, a.world};
+    }
+};
 
 }  // namespace
