@@ -7,6 +7,12 @@ the Random123 known-answer vectors and by the EKF oracle on the 2x2 feature bloc
 Tolerances: fp64 1e-9 (values) -- the device and NumPy evaluate the same formulas on the same Philox
 words, only libm differs; fp32 2e-4 relative to the quantity's scale.  Index work (ancestor tables,
 gather sources, record exchange) must be exact.
+
+NOT COVERED HERE: every run of this module starts at a heading of -0.2 .. 0.4, steers within +-0.25 rad and takes its
+bearings from observe(), which does not bring them into [-pi, pi].  No heading reaches +-pi, and the bearing innovation of an
+observation against its own landmark is noise-sized before the wrap, so none of the wrap_pi calls of the FastSLAM kernels
+changes a value that matters on these scenes (pinned in tests/test_wrap_scenes_cpu.py).  Headings across the seam, wrapped
+bearings and landmarks where the fp32 atan2 branches are in tests/test_gpu_pf_wrap.py, for every form of the step.
 """
 import math
 
