@@ -12,7 +12,8 @@ NOT COVERED HERE: every run of this module starts at a heading of -0.2 .. 0.4, s
 bearings from observe(), which does not bring them into [-pi, pi].  No heading reaches +-pi, and the bearing innovation of an
 observation against its own landmark is noise-sized before the wrap, so none of the wrap_pi calls of the FastSLAM kernels
 changes a value that matters on these scenes (pinned in tests/test_wrap_scenes_cpu.py).  Headings across the seam, wrapped
-bearings and landmarks where the fp32 atan2 branches are in tests/test_gpu_pf_wrap.py, for every form of the step.
+bearings and landmarks where the fp32 atan2 branches are in tests/test_gpu_pf_wrap.py, for every form of the step.  The bounds
+here are relative to the filter's largest entry; tests/test_gpu_pf_records.py holds lm_update / lm_init to per-record rounding bounds.
 """
 import math
 
