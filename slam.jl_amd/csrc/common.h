@@ -73,7 +73,7 @@ static inline int slam_exp_env(const char* name, int dflt) {
 constexpr int SLAM_XFLAGS_MASK = ~0;
 #else
 static inline int slam_exp_env(const char*, int dflt) { return dflt; }
-constexpr int SLAM_XFLAGS_MASK = 4 | 8 | 16 | 32 | 64 | 128 | 512;
+constexpr int SLAM_XFLAGS_MASK = 4 | 8 | 16 | 32 | 64 | 128 | 512 | 65536;
 #endif
 
 struct TimingPair {

@@ -686,6 +686,25 @@ __device__ __forceinline__ void read_frags_d(const DdCtx& c, const char* sm, int
         : "v"(ya), "v"(xa)
         : "memory");
 }
+// The same nine reads WITHOUT their wait, and the wait that belongs to them: the registers are operands of the wait, so whatever
+// uses the fragments stands behind it in the instruction stream as well.
+__device__ __forceinline__ void issue_frags_d(const DdCtx& c, const char* sm, int buf, DdFrags& f) {
+    const unsigned base = lds_addr(sm) + buf * DMA_BUF + c.l31 * 32 + ((c.lh ^ (c.l31 >> 3)) & 1) * 16;
+    const unsigned ya = base + IMG_CHUNK + (32 * c.wc) * 32, xa = base + (64 * c.wr) * 32;
+    asm volatile(
+        "ds_read_b128 %0, %9\n\tds_read_b128 %1, %9 offset:4096\n\tds_read_b128 %2, %9 offset:8192\n\t"
+        "ds_read_b128 %3, %10\n\tds_read_b128 %4, %10 offset:4096\n\tds_read_b128 %5, %10 offset:8192\n\t"
+        "ds_read_b128 %6, %10 offset:1024\n\tds_read_b128 %7, %10 offset:5120\n\tds_read_b128 %8, %10 offset:9216"
+        : "=&v"(f.a[0]), "=&v"(f.a[1]), "=&v"(f.a[2]), "=&v"(f.b[0]), "=&v"(f.b[1]), "=&v"(f.b[2]), "=&v"(f.b1[0]), "=&v"(f.b1[1]), "=&v"(f.b1[2])
+        : "v"(ya), "v"(xa)
+        : "memory");
+}
+__device__ __forceinline__ void wait_frags_d(DdFrags& f) {
+    asm volatile("s_waitcnt lgkmcnt(0)"
+                 : "+v"(f.a[0]), "+v"(f.a[1]), "+v"(f.a[2]), "+v"(f.b[0]), "+v"(f.b[1]), "+v"(f.b[2]), "+v"(f.b1[0]), "+v"(f.b1[1]), "+v"(f.b1[2])
+                 :
+                 : "memory");
+}
 __device__ __forceinline__ void mfma_frags_d(const DdFrags& f, f32x16 (&acc)[2]) {
 #pragma unroll
     for (int rb = 0; rb < 2; ++rb) {
@@ -770,6 +789,111 @@ __device__ __forceinline__ void dd_stream_dma(DdCtx& c, const int2* __restrict__
     wait_vm<0>();                      // (nothing of this path is in flight when the diagonal tiles take the LDS array over)
 }
 
+// dd_stream_dma with TWO fragment sets in the steady state: the same buffers, the same requests in the same queue order, the
+// same products in the same order -- what moves is the fragment reads.  The P patch is needed only behind the last chunk and
+// when it is requested does not matter (measured at steps 2, 3, 4 and 6), so it is requested at step NCH - 2 and until then its
+// 32 registers carry a second fragment set: in steps ch = 0 .. NCH - 3 the reads of chunk ch + 1 are issued right behind the
+// barrier that makes that chunk visible and IN FRONT of the MFMAs of chunk ch, and land under them.  A step of the steady state
+// therefore starts with its barrier:
+//     [wait: chunk ch + 1 landed; lgkmcnt(0): MY reads of chunk ch are complete] barrier
+//     reads of chunk ch + 1 -> the other set;  request of chunk ch + 3 into the buffer of chunk ch;  MFMAs of chunk ch
+// The buffer of chunk ch is refilled behind a barrier in front of which EVERY wave has waited for its reads of that chunk
+// (wait_frags_d, lgkmcnt(0)): the invariant of the three buffers, spelled out.  Steps NCH - 2 and NCH - 1 run as in
+// dd_stream_dma (one set; the P patch lives only there), the first reads of a tile (chunk 0) stay exposed.
+//   The queue of a wave, tile after tile (D = a chunk's three pieces, P / S = the patch's 32 loads / stores):
+//     D0 | P D1 | D2 S | D3 | D4 | .. | D(NCH) = the next tile's D0 | P D1 | D2 S | ..
+// and the counts (lower bounds of what was issued behind the chunk waited for, see above): steps 0 and 1: 3 + 32 (S), 3 on a
+// workgroup's first tile; steps 2 .. NCH - 3: 3; step NCH - 2: 32 (P) + 3 if a tile follows; step NCH - 1: 32 + 3 if a tile
+// follows, else everything.
+template <int NCH>
+__device__ __forceinline__ void dd_stream_dma_ovl(DdCtx& c, const int2* __restrict__ list, int L, int nper, int& slot, char* sm,
+                                                  unsigned* __restrict__ ctr, int wave, char* cw) {
+    static_assert(NCH >= 5, "");
+    constexpr int RD = NCH - 3;        // the step behind whose barrier the next tile's first chunk is requested (the last two-set step)
+    auto fetch = [&](int sl) { return sl < L ? list[sl] : make_int2(-1, -1); };
+    int2 tile = fetch(slot);
+    int2 next = make_int2(-1, -1);
+    int next_slot = slot + nper;
+    unsigned claimed = 0;
+    f32x16 acc[2];
+#pragma unroll
+    for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[rb][r] = 0.0f;
+    dma_chunk(c, tile, 0, sm, 0, wave);
+    dma_chunk(c, tile, 1, sm, 1, wave);
+    dma_chunk(c, tile, 2, sm, 2, wave);
+    wait_vm<6>();
+    bare_barrier();
+    int base = 0;                      // the buffer that holds chunk 0 of the current tile
+    bool first = true;
+    for (;;) {
+        bool next_off = false;
+        DdFrags fr[2];
+        asm volatile("" : "+s"(base));                                          // (kept a run-time value on the first tile too: with it folded, the compiler keeps every buffer's read address in a register of its own and spills)
+        __builtin_amdgcn_sched_barrier(0);
+        issue_frags_d(c, sm, base, fr[0]);                                      // (chunk 0 is visible since the previous barrier)
+        static_for<0, NCH - 2>([&](auto CH) {                                   // two fragment sets
+            constexpr int ch = decltype(CH)::value;
+            const int buf = (base + ch) % 3;
+            __builtin_amdgcn_sched_barrier(0);
+            if (ch == RD && threadIdx.x == 0) asm_lds_store_u32(cw, claimed);
+            if (ch <= 1) {                                                      // behind chunk ch + 1: the previous tile's stores and chunk ch + 2
+                if (first) wait_vm<3>();
+                else wait_vm<35>();
+            } else wait_vm<3>();                                                // (chunk ch + 2 <= NCH - 1 is this tile's)
+            wait_frags_d(fr[ch & 1]);                                           // my reads of chunk ch are complete: behind the barrier its buffer is free
+            bare_barrier();
+            issue_frags_d(c, sm, (base + ch + 1) % 3, fr[(ch + 1) & 1]);
+            if (ch == 0 && threadIdx.x == 0) claimed = __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (ch == RD) {
+                next_slot = nper + __builtin_amdgcn_readfirstlane((int)asm_lds_load_u32(cw));
+                next = fetch(next_slot);
+                next_off = next.x >= 0 && next.x != next.y;
+            }
+            if (ch + 3 < NCH) dma_chunk(c, tile, ch + 3, sm, buf, wave);
+            else if (next_off) dma_chunk(c, next, ch + 3 - NCH, sm, buf, wave);
+            __builtin_amdgcn_sched_barrier(0);
+            mfma_frags_d(fr[ch & 1], acc);
+        });
+        {                                                                       // step NCH - 2: the P tile is requested, one fragment set from here
+            constexpr int ch = NCH - 2;
+            float pold[2][16];
+            __builtin_amdgcn_sched_barrier(0);
+            // (the patch's lane offsets come from the lane number taken HERE: derived from threadIdx.x they are reloaded from the
+            //  kernel's entry spill, a scratch access and a vmcnt(0) in the middle of the stream)
+            DdCtx cp = c;
+            unsigned lane;
+            asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane));
+            cp.l31 = lane & 31;
+            cp.lh = lane >> 5;
+            load_p_mfma(cp, tile.x * TILE, tile.y * TILE, pold);
+            __builtin_amdgcn_sched_barrier(0);
+            wait_frags_d(fr[ch & 1]);
+            mfma_frags_d(fr[ch & 1], acc);
+            if (next_off) wait_vm<35>();                                        // behind chunk NCH - 1: the next tile's chunk 0 and the P loads
+            else wait_vm<32>();
+            bare_barrier();
+            if (next_off) dma_chunk(c, next, 1, sm, (base + ch) % 3, wave);
+            __builtin_amdgcn_sched_barrier(0);
+            read_frags_d(c, sm, (base + ch + 1) % 3, fr[(ch + 1) & 1]);         // step NCH - 1
+            mfma_frags_d(fr[(ch + 1) & 1], acc);
+            if (next_off) wait_vm<35>();                                        // behind the next tile's chunk 0: the P loads and its chunk 1
+            else wait_vm<0>();
+            bare_barrier();
+            if (next_off) dma_chunk(c, next, 2, sm, (base + ch + 1) % 3, wave);
+            __builtin_amdgcn_sched_barrier(0);                                  // (the chunk request stays in front of the tile's stores)
+            store_p_mfma(cp, tile.x * TILE, tile.y * TILE, pold, acc);
+        }
+        slot = next_slot;
+        if (!next_off) break;
+        tile = next;
+        base = (base + NCH) % 3;
+        first = false;
+    }
+    wait_vm<0>();                      // (nothing of this path is in flight when the diagonal tiles take the LDS array over)
+}
+
 // As dd_stream: processes list[slot], list[slot + nper], ... while they are off-diagonal; NCH = kp / 16 (>= 2).  On
 // entry gx/gy hold the request for chunk 0 of the first tile.  On return `slot` is the first unprocessed position;
 // nothing is in flight for it (the diagonal tiles that follow use the fp32 pipeline and request their own panels).
@@ -825,7 +949,7 @@ __device__ __forceinline__ void dd_stream_b(DdCtx& c, const int2* __restrict__ l
 // wave that moves on to the next tile's MFMAs lets its stores drain behind them.  The first tile is
 // peeled so that the loop header sees the same load/store history on both of its incoming edges and the
 // compiler can emit counted vmcnt waits for the panel chunk instead of vmcnt(0).
-template <int STREAM = 0, int POFF = 2, bool BF = false>   // STREAM = chunks per tile (2..4) for the streaming path, 0: dd_tile only; BF: split-bf16 streaming path where kp allows
+template <int STREAM = 0, int POFF = 2, bool BF = false, bool OVL = false>   // STREAM = chunks per tile (2..4) for the streaming path, 0: dd_tile only; BF: split-bf16 streaming path where kp allows; OVL: its LDS-DMA pipeline with two fragment sets (dd_stream_dma_ovl)
 __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(4, 4))) void downdate_f32_mfma(float* __restrict__ P, int ld, int n,
                                                                  const float* __restrict__ X, const float* __restrict__ Y,
                                                                  int pitch, int kp, const int2* __restrict__ tiles, int L,
@@ -879,7 +1003,13 @@ __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(4, 4))
         if (tile.x != tile.y && !(c.xflags & 512)) {         // the LDS-DMA pipeline, chunks two steps ahead (SLAMHIP_X bit 512: round 3's register-staged pipeline below)
             static_assert(sizeof(smem) == 3 * DMA_BUF, "three 24 KB chunk buffers");
             char* cw = reinterpret_cast<char*>(&dma_claim_word[0]);
-            switch (kp / KB) {
+            if constexpr (OVL) switch (kp / KB) {
+                case 8: dd_stream_dma_ovl<8>(c, list, L, nper, slot, sm, ctr, wave, cw); break;
+                case 7: dd_stream_dma_ovl<7>(c, list, L, nper, slot, sm, ctr, wave, cw); break;
+                case 6: dd_stream_dma_ovl<6>(c, list, L, nper, slot, sm, ctr, wave, cw); break;
+                default: dd_stream_dma_ovl<5>(c, list, L, nper, slot, sm, ctr, wave, cw); break;
+            }
+            else switch (kp / KB) {
                 case 8: dd_stream_dma<8, DD_DMA_PCH8>(c, list, L, nper, slot, sm, ctr, wave, cw); break;
                 case 7: dd_stream_dma<7, 2>(c, list, L, nper, slot, sm, ctr, wave, cw); break;
                 case 6: dd_stream_dma<6, 2>(c, list, L, nper, slot, sm, ctr, wave, cw); break;
@@ -1278,7 +1408,11 @@ int launch_downdate(slam_ekf* h, int kp_total, const void* X, const void* Y, int
                 int wgs = dyn ? per_xcd : L;
                 if (wgs > L) wgs = L;
                 if (wgs < 1) wgs = 1;
-                if (dyn) {                 // (the counters were zeroed by the W1 kernel that wrote the image: ekf_update.hip)
+                if (dyn && !(h->xflags & 65536)) {     // (the counters were zeroed by the W1 kernel that wrote the image: ekf_update.hip)
+                    hipLaunchKernelGGL((downdate_f32_mfma<4, 3, true, true>), dim3(8 * wgs), dim3(NTHREADS), 0, h->stream,
+                                       (float*)h->P, h->ld, n, (const float*)X, (const float*)Y, pitch, kp_total, lst, L,
+                                       h->d_status, h->xflags, dcount, joseph, IMGARGS_CLAIM);
+                } else if (dyn) {          // SLAMHIP_X bit 65536: the LDS-DMA pipeline with one fragment set (dd_stream_dma)
                     hipLaunchKernelGGL((downdate_f32_mfma<4, 3, true>), dim3(8 * wgs), dim3(NTHREADS), 0, h->stream,
                                        (float*)h->P, h->ld, n, (const float*)X, (const float*)Y, pitch, kp_total, lst, L,
                                        h->d_status, h->xflags, dcount, joseph, IMGARGS_CLAIM);
