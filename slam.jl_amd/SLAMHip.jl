@@ -14,11 +14,15 @@ module SLAMHip
 
 export SlamState, EKFSlamState, set_state!, predict, update, add_features, associate,
        compute_association, predict_observation, mpi_to_pi,
-       ekf_predict!, ekf_update!, augment!, observe!, cov_block, cov_diag, landmark_blocks, gate_mode!, gate_info, state_written!, remove_features!, find_duplicates, merge_landmarks!, feature_ellipses, vehicle_ellipse,
+       ekf_predict!, ekf_update!, augment!, observe!, cov_block, cov_diag, landmark_blocks, gate_mode!, gate_info, state_written!, remove_features!, find_duplicates, merge_landmarks!, transform!, feature_ellipses, vehicle_ellipse,
        PFSlamState, set_pose!, init_landmarks!, pf_predict!, update_known!, step!, step_async!, step_async_batch!, step_unknown!, flush!,
        resample!, mean_pose, weights, particles, pf_map, pf_best_particle, peer_blob, attach_peers!, peer_selftest, detach_peers!, comm_info
 
 const libslamhip = get(ENV, "SLAMHIP_LIB", joinpath(@__DIR__, "libslamhip.so"))
+# the companion library of include/slamhip_frame.h (the rigid frame change); it links against libslamhip.so and lies beside it
+# (opened at the first transform!; it is linked against the libslamhip.so beside it: with SLAMHIP_LIB pointing at another build,
+#  point SLAMHIP_FRAME_LIB at a companion linked against THAT build, or do not call transform!)
+const libslamhip_frame = get(ENV, "SLAMHIP_FRAME_LIB", joinpath(@__DIR__, "libslamhip_frame.so"))
 
 const SLAM_OK = Cint(0)
 const SLAM_PF_HALTED = Cint(1)
@@ -273,6 +277,17 @@ function merge_landmarks!(s::EKFSlamState, pairs::AbstractMatrix{<:Integer}; Rc 
     new_index
 end
 
+"""
+    transform!(s, tx, ty, theta) -> s
+
+Express the whole state in another frame, in place on the device (slam_ekf_transform): every position becomes
+R(theta) p + (tx, ty), the heading mpi_to_pi(phi + theta), cov becomes T cov T' with T = blockdiag(R, 1, R, R, ...).  Enqueued.
+"""
+function transform!(s::EKFSlamState, tx::Real, ty::Real, theta::Real)
+    check(ccall((:slam_ekf_transform, libslamhip_frame), Cint, (Ptr{Cvoid}, Cdouble, Cdouble, Cdouble), handle(s), tx, ty, theta))
+    s
+end
+
 "feature_ellipses(x, cov) of the browser monitor (sim/browser/wsserver.jl:72-85): 5 x N [cx; cy; rx; ry; phi], on the device."
 function feature_ellipses(s::EKFSlamState)
     out = Matrix{Float64}(undef, 5, nlandmarks(s))
@@ -458,6 +473,17 @@ function step_unknown!(s::PFSlamState, V::Real, G::Real, wheelbase::Real, Q::Abs
                 s.handle, V, G, wheelbase, colmajor4(Q), dt, pairs64(z), size(z, 2), colmajor4(R), gate1, gate2,
                 Ptr{Int32}(C_NULL), out))
     out
+end
+
+"""
+    transform!(state, tx, ty, theta) -> state
+
+Express the filter in another frame (slam_pf_transform): every particle's pose and every landmark record in use through
+p <- R(theta) p + (tx, ty), Pf <- R Pf R'; the log-weights and the RNG step are untouched.  Enqueued.
+"""
+function transform!(s::PFSlamState, tx::Real, ty::Real, theta::Real)
+    check(ccall((:slam_pf_transform, libslamhip_frame), Cint, (Ptr{Cvoid}, Cdouble, Cdouble, Cdouble), s.handle, tx, ty, theta))
+    s
 end
 
 """

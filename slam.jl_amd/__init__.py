@@ -13,7 +13,8 @@ from ._lib import NotPositiveDefinite, SlamHipError, device_count  # noqa: F401
 from .ekf import (DeviceRef, EKFSlamState, SlamState, add_features, associate, augment_,  # noqa: F401
                   compute_association, ekf_predict_, ekf_update_, mpi_to_pi, predict, predict_observation,
                   observe, remove_features, remove_features_, removal_maps, update,
-                  find_duplicates, merge_features, merge_features_, merge_in_batches)
+                  find_duplicates, merge_features, merge_features_, merge_in_batches,
+                  rigid_fit, transform_features, transform_features_)
 from .pf import (FastSLAM, PFShard, PFSlamState, TorchComm, attach_local_peers, philox_uniform, shared_page,  # noqa: F401
                  small)
 from . import sim  # noqa: F401

@@ -166,6 +166,45 @@ for _name, (_res, _args) in SIGNATURES.items():
     _fn.argtypes = _args
 
 
+# ---- the companion library: the rigid frame change (include/slamhip_frame.h) -----------------------------------------------
+# libslamhip.so exports exactly what its two headers declare; the frame change lives beside it in libslamhip_frame.so, which
+# links against libslamhip.so (run path $ORIGIN) and works on its handles.  It is opened at the first transform, not at
+# import: a tree with only libslamhip.so built imports and runs as before.
+FRAME_LIB_PATH = os.path.join(_HERE, "libslamhip_frame.so")
+
+#: every symbol include/slamhip_frame.h declares
+FRAME_SIGNATURES = {
+    "slam_ekf_transform": (C.c_int, [_h, C.c_double, C.c_double, C.c_double]),
+    "slam_pf_transform": (C.c_int, [_h, C.c_double, C.c_double, C.c_double]),
+}
+
+_frame = None
+
+
+def frame_lib():
+    """libslamhip_frame.so, opened on first use.  No fallback: missing or unloadable is an ImportError.  With SLAMHIP_LIBRARY
+    pointing elsewhere the handles belong to THAT library while the companion is linked against libslamhip.so, whose copy
+    of the helpers it would run on them: refused."""
+    global _frame
+    if _frame is not None:
+        return _frame
+    if os.path.abspath(LIB_PATH) != os.path.join(_HERE, "libslamhip.so"):
+        raise ImportError(f"libslamhip_frame.so is linked against {os.path.join(_HERE, 'libslamhip.so')}; the handles of "
+                          f"{LIB_PATH} (SLAMHIP_LIBRARY) cannot be passed to it")
+    if not os.path.exists(FRAME_LIB_PATH):
+        raise ImportError(f"{FRAME_LIB_PATH} is missing: build it with `make -C slam.jl_amd/csrc`.  slam.jl_amd has no CPU fallback.")
+    try:
+        fl = C.CDLL(FRAME_LIB_PATH)
+    except OSError as e:  # pragma: no cover - depends on the machine
+        raise ImportError(f"cannot load {FRAME_LIB_PATH}: {e}.  slam.jl_amd has no CPU fallback.") from e
+    for name, (res, args) in FRAME_SIGNATURES.items():
+        fn = getattr(fl, name)
+        fn.restype = res
+        fn.argtypes = args
+    _frame = fl
+    return fl
+
+
 def last_error() -> str:
     msg = lib.slam_last_error()
     return msg.decode("utf-8", "replace") if msg else ""

@@ -1,6 +1,6 @@
 // pf_internal.h -- the FastSLAM particle path: state, control blocks and the host-side pieces shared by its translation
 // units (pf_legacy.hip: the rank-local kernels and entry points; pf_unknown.hip: the unknown-correspondence step; pf_auto.hip: the step without the host; pf_peers.hip: the
-// sharding behind the C ABI; pf_map.hip: the map and particle read-outs).  Device code common to the kernels: pf_device.h.
+// sharding behind the C ABI; pf_map.hip: the map and particle read-outs; pf_transform.hip: the rigid frame change).  Device code common to the kernels: pf_device.h.
 #pragma once
 #include <stdlib.h>
 #include <unistd.h>
@@ -259,6 +259,7 @@ int pf_auto_wait(slam_pf* h, long long target);   // poll the mirror until step 
 const char* pf_error_text(long long code);
 // pf_legacy.hip
 double pf_take_pending(slam_pf* h);        // the normalisation shift slam_pf_normalize deferred (and forget it)
+int pf_flush_pending(slam_pf* h);          // ... applied to the log-weights now (enqueued), as slam_pf_download does
 int pf_materialise(slam_pf* h);            // every landmark to (buffer h->cur, identity table); collective with peers attached
 int pf_stage(slam_pf* h, const double* z, const int32_t* ids, int m, const double** d_z, const int32_t** d_i);   // observations into the next pinned staging slot
 int pf_stage_done(slam_pf* h);             // record the slot's event behind the kernel that reads it

@@ -837,7 +837,7 @@ double pf_take_pending(slam_pf* h) {
     return p;
 }
 
-static int pf_flush_pending(slam_pf* h) {
+int pf_flush_pending(slam_pf* h) {
     if (!h->has_pending) return SLAM_OK;
     const double shift = pf_take_pending(h);
     PF_DISPATCH(h,

@@ -140,6 +140,31 @@ def mpi_to_pi(phi):
     return phi
 
 
+def rigid_fit(src, dst):
+    """The closed-form 2-D least-squares rigid fit (rotation and translation, no scale) of the points ``src`` onto ``dst``
+    ([2, k] or [k, 2] each, k >= 2; a 2 x 2 array is ALWAYS read as [2, k], one point per column):
+    theta = atan2(sum cross, sum dot) of the two centred point sets, t = the centroid of
+    dst minus the rotated centroid of src.  Returns ``(tx, ty, theta)`` with dst ~ R(theta) src + t.  Fewer than two
+    points, or all points of either set coincident: ValueError."""
+    def pts(a):
+        a = np.asarray(a, dtype=np.float64)
+        if a.ndim != 2 or 2 not in a.shape:
+            raise ValueError("points must be [2, k] or [k, 2]")
+        return a if a.shape[0] == 2 else a.T                 # (a 2 x 2 array is read as [2, k])
+    a, b = pts(src), pts(dst)
+    if a.shape != b.shape:
+        raise ValueError("src and dst disagree on the number of points")
+    if a.shape[1] < 2:
+        raise ValueError("a rigid fit needs at least two points")
+    ca, cb = a.mean(axis=1, keepdims=True), b.mean(axis=1, keepdims=True)
+    da, db = a - ca, b - cb
+    if not (np.sum(da * da) > 0.0 and np.sum(db * db) > 0.0):
+        raise ValueError("coincident points do not determine a rotation")
+    theta = math.atan2(float(np.sum(da[0] * db[1] - da[1] * db[0])), float(np.sum(da[0] * db[0] + da[1] * db[1])))
+    c, s = math.cos(theta), math.sin(theta)
+    return float(cb[0, 0] - (c * ca[0, 0] - s * ca[1, 0])), float(cb[1, 0] - (s * ca[0, 0] + c * ca[1, 0])), theta
+
+
 class SlamState:
     """``abstract SlamState`` (src/common.jl:22)."""
 
@@ -436,6 +461,27 @@ class EKFSlamState(SlamState):
 
         return merge_in_batches(self.N, pairs, call)
 
+    def transform(self, tx, ty, theta):
+        """Express the whole state in another frame, in place on the device (slam_ekf_transform): every position becomes
+        R(theta) p + (tx, ty), the heading mpi_to_pi(phi + theta), cov becomes T cov T' with T = blockdiag(R, 1, R, R, ...).
+        Enqueued on the state's stream; nothing is downloaded."""
+        check(_lib.frame_lib().slam_ekf_transform(self._h, float(tx), float(ty), float(theta)))
+
+    def align(self, ids, xy, apply=True):
+        """Fit the rigid transform (no scale) that carries the means of the landmarks ``ids`` (1-based) onto the surveyed
+        positions ``xy`` ([2, k] or [k, 2]; for two landmarks a 2 x 2 array is read as [2, k]: one point per column) in the
+        least-squares sense (rigid_fit) and, unless ``apply`` is False, move
+        the state into that frame (transform).  Only x is downloaded.  Returns ``(tx, ty, theta)``."""
+        ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+        x = np.asarray(self.download("x"), dtype=np.float64)
+        f = 3 + 2 * (ids - 1)
+        if ids.size and (ids.min() < 1 or ids.max() > self.N):
+            raise ValueError("landmark id out of range")
+        tx, ty, theta = rigid_fit(np.stack([x[f], x[f + 1]]), xy)
+        if apply:
+            self.transform(tx, ty, theta)
+        return tx, ty, theta
+
     def observe(self, z, R, gate1, gate2, form="cholesky"):
         """associate -> update -> add_features (sim/ekfslam-sim.jl:114-120) in one library call with no host
         round trip between the gating and the update.  Returns the association vector
@@ -627,6 +673,20 @@ def remove_features(state: EKFSlamState, ids):
 def remove_features_(state, ids):
     """In-place name (Julia: ``remove_features!``); returns the index map as well."""
     return _state_of(state).remove_landmarks(ids)
+
+
+def transform_features(state: EKFSlamState, tx, ty, theta):
+    """Express the state in another frame -> (x, P) (see EKFSlamState.transform)."""
+    st = _state_of(state)
+    st.transform(tx, ty, theta)
+    return st.x, st.cov
+
+
+def transform_features_(state, tx, ty, theta):
+    """In-place name (Julia: ``transform!``); returns the state."""
+    st = _state_of(state)
+    st.transform(tx, ty, theta)
+    return st
 
 
 def find_duplicates(state: EKFSlamState, gate, cap=1024):

@@ -28,8 +28,8 @@ import sys
 
 import numpy as np
 
-from ._lib import SLAM_F32, SLAM_F64, SLAM_PF_HALTED, SLAM_PF_PEER_BLOB_BYTES, check, lib
-from .ekf import _obs, _small, _ptr
+from ._lib import SLAM_F32, SLAM_F64, SLAM_PF_HALTED, SLAM_PF_PEER_BLOB_BYTES, check, frame_lib, lib
+from .ekf import _obs, _small, _ptr, rigid_fit
 
 __all__ = ["PFShard", "PFSlamState", "FastSLAM", "philox_uniform", "small", "shared_page", "attach_local_peers",
            "finalise_map", "ellipse_axes", "MapSnapshot"]
@@ -427,6 +427,12 @@ class PFShard:
         out = np.empty(self.n)
         check(lib.slam_pf_get_weights(self._h, _ptr(out)))
         return out
+
+    def transform(self, tx, ty, theta):
+        """Express this shard's particles in another frame (slam_pf_transform): every pose and every landmark record in
+        use through p <- R(theta) p + (tx, ty), Pf <- R Pf R'; log-weights and the RNG step are untouched.  Enqueued;
+        collective with peers attached."""
+        check(frame_lib().slam_pf_transform(self._h, float(tx), float(ty), float(theta)))
 
     # -- the map without downloading the particles (slam_pf_map_sums / slam_pf_get_map / slam_pf_get_particle) ---
     @staticmethod
@@ -864,6 +870,22 @@ class FastSLAM:
         """The map: [cnt, 8] = {mass, mean x, mean y, Cxx, Cxy, Cyy, count, 0} per landmark (``ids`` 1-based, None: all),
         the moment-matched Gaussian of the particles' mixture (see finalise_map).  Collective for a sharded filter."""
         return finalise_map(self.map_sums(ids))
+
+    def transform(self, tx, ty, theta):
+        """Express the filter in another frame: every rank calls it on its shard (PFShard.transform)."""
+        self.shard.transform(tx, ty, theta)
+
+    def align(self, ids, xy, apply=True):
+        """Fit the rigid transform (no scale) that carries the map() means of the landmarks ``ids`` (1-based) onto the
+        surveyed positions ``xy`` ([2, k] or [k, 2]; 2 x 2 is read as [2, k]) in the least-squares sense and, unless ``apply`` is False, move the
+        filter into that frame.  Returns ``(tx, ty, theta)``.  Collective for a sharded filter."""
+        m = self.map(np.asarray(ids, dtype=np.int32).reshape(-1))
+        if m.shape[0] and not np.all(m[:, 0] > 0.0):
+            raise ValueError("a named landmark has no particle that holds it")
+        tx, ty, theta = rigid_fit(m[:, 1:3].T, xy)
+        if apply:
+            self.transform(tx, ty, theta)
+        return tx, ty, theta
 
     def best_particle(self):
         """The particle with the largest log-weight of the whole filter (lowest global id on a tie):
