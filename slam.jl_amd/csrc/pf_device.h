@@ -812,14 +812,27 @@ __device__ __forceinline__ void proposal_core(T* __restrict__ pose, const LmView
         g00 = g00 - (w00 * w00 + w01 * w01);
         g01 = g01 - (w00 * w10 + w01 * w11);
         g11 = g11 - (w10 * w10 + w11 * w11);
+        // A guard: g -= w w' keeps an absolute error of eps of what Sig started from, so a Sig collapsed by 1 / eps is rounding noise
+        // of either sign, and a negative pivot of S or of chol(Sig) would make the pose NaN.  Sig is kept positive semi-definite
+        // (S >= Sf whatever the rounding did); a positive definite Sig keeps its bits.  (A NaN entry becomes 0; mu carries the NaN on.)
+        g00 = fmax(g00, (T)0);
+        g11 = fmax(g11, (T)0);
+        if constexpr (kFast<T>) {                          // (branch-free: one v_sqrt_f32 and a median of three)
+            const T glim = m_sqrt<T>(g00 * g11);
+            g01 = fmin(fmax(g01, -glim), glim);
+        } else {
+            const T gdet = g00 * g11;
+            if (g01 * g01 > gdet) g01 = copysign(sqrt(gdet), g01);
+        }
         lw += (T)-0.5 * (y0 * y0 + y1 * y1) - m_log<T>(u00 * u11) - (T)1.8378770664093453;
     }
     // w ~ N(mu, Sig), the control, the pose
     T e1, e2;
     normals2<T>((uint64_t)(first + p), step, STREAM_PREDICT, seed, e1, e2);
+    // chol(Sig): a pivot that is not positive means "no spread left in this direction" -- the draw is the mean there
     const T l00 = sqrt(g00);
-    const T l10 = g01 / l00;
-    const T l11 = sqrt(g11 - l10 * l10);
+    const T l10 = l00 > (T)0 ? g01 / l00 : (T)0;
+    const T l11 = sqrt(fmax(g11 - l10 * l10, (T)0));
     const T w0 = mu0 + l00 * e1;
     const T w1 = mu1 + l10 * e1 + l11 * e2;
     const T Vn = V + lq00 * w0;
