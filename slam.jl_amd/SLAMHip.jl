@@ -14,7 +14,7 @@ module SLAMHip
 
 export SlamState, EKFSlamState, set_state!, predict, update, add_features, associate,
        compute_association, predict_observation, mpi_to_pi,
-       ekf_predict!, ekf_update!, augment!, observe!, cov_block, cov_diag, landmark_blocks, gate_mode!, gate_info, state_written!, remove_features!, find_duplicates, merge_landmarks!, transform!, feature_ellipses, vehicle_ellipse,
+       ekf_predict!, ekf_update!, augment!, observe!, cov_block, cov_diag, landmark_blocks, gate_mode!, gate_info, state_written!, remove_features!, find_duplicates, merge_landmarks!, transform!, join!, submap, feature_ellipses, vehicle_ellipse,
        PFSlamState, set_pose!, init_landmarks!, pf_predict!, update_known!, step!, step_async!, step_async_batch!, step_unknown!, flush!,
        resample!, mean_pose, weights, particles, pf_map, pf_best_particle, peer_blob, attach_peers!, peer_selftest, detach_peers!, comm_info
 
@@ -23,6 +23,8 @@ const libslamhip = get(ENV, "SLAMHIP_LIB", joinpath(@__DIR__, "libslamhip.so"))
 # (opened at the first transform!; it is linked against the libslamhip.so beside it: with SLAMHIP_LIB pointing at another build,
 #  point SLAMHIP_FRAME_LIB at a companion linked against THAT build, or do not call transform!)
 const libslamhip_frame = get(ENV, "SLAMHIP_FRAME_LIB", joinpath(@__DIR__, "libslamhip_frame.so"))
+# the companion library of include/slamhip_join.h (map joining), same arrangement (opened at the first join!)
+const libslamhip_join = get(ENV, "SLAMHIP_JOIN_LIB", joinpath(@__DIR__, "libslamhip_join.so"))
 
 const SLAM_OK = Cint(0)
 const SLAM_PF_HALTED = Cint(1)
@@ -52,12 +54,13 @@ new feature, src/ekf.jl:108-109).
 """
 mutable struct EKFSlamState{T<:Union{Float32,Float64}} <: SlamState
     handle::Ptr{Cvoid}
+    device::Int                                   # the device the handle lives on (submap creates its local map there)
     function EKFSlamState{T}(x::AbstractVector, cov::AbstractMatrix;
                              max_landmarks::Integer = max(64, length(x) - 3), device::Integer = 0) where {T}
         h = Ref{Ptr{Cvoid}}(C_NULL)
         check(ccall((:slam_ekf_create, libslamhip), Cint, (Ref{Ptr{Cvoid}}, Cint, Cint, Cint),
                     h, T === Float32 ? SLAM_F32 : SLAM_F64, max_landmarks, device))
-        s = new{T}(h[])
+        s = new{T}(h[], Int(device))
         finalizer(s) do st
             ccall((:slam_ekf_destroy, libslamhip), Cint, (Ptr{Cvoid},), getfield(st, :handle))
         end
@@ -286,6 +289,45 @@ R(theta) p + (tx, ty), the heading mpi_to_pi(phi + theta), cov becomes T cov T' 
 function transform!(s::EKFSlamState, tx::Real, ty::Real, theta::Real)
     check(ccall((:slam_ekf_transform, libslamhip_frame), Cint, (Ptr{Cvoid}, Cdouble, Cdouble, Cdouble), handle(s), tx, ty, theta))
     s
+end
+
+"""
+    submap(s, max_landmarks) -> EKFSlamState
+
+A fresh local map for `join!`: same element type and same device as `s`, pose (0, 0, 0), no landmark, cov = 0.  Its frame is the
+vehicle pose of `s` for as long as `s` neither moves nor observes.
+"""
+submap(s::EKFSlamState{T}, max_landmarks::Integer) where {T} =
+    EKFSlamState{T}(zeros(T, 3), zeros(T, 3, 3); max_landmarks = max_landmarks, device = getfield(s, :device))
+
+"""
+    join!(a, b; merge_gate = nothing, Rc = nothing) -> first_new  |  (first_new, new_index)
+
+Map joining on the device (slam_ekf_join): the local map `b`, whose frame is `a`'s vehicle pose (`submap`), is appended to `a`:
+the vehicle is composed with `b`'s, `b`'s landmark j becomes landmark N_a + j, cov becomes F cov F' + G cov_b G'.  `b` is only
+read.  `first_new` is the id in `a` of `b`'s first landmark.  With `merge_gate` the overlap is fused afterwards
+(`find_duplicates(a, merge_gate)`, then `merge_landmarks!` on at most 8 disjoint pairs, round after round until no pair is found)
+and the composed `new_index` (one entry per landmark of the joined map) is returned as well.
+"""
+function join!(a::EKFSlamState{T}, b::EKFSlamState{T}; merge_gate = nothing, Rc = nothing) where {T}
+    first = Ref{Int32}(0)
+    check(ccall((:slam_ekf_join, libslamhip_join), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ref{Int32}), handle(a), handle(b), first))
+    merge_gate === nothing && return Int(first[])
+    cur = collect(Int32, 1:nlandmarks(a))
+    while true
+        pairs, count = find_duplicates(a, merge_gate)
+        count == 0 && break
+        batch = Vector{Int32}[]
+        busy = Set{Int32}()
+        for k in 1:size(pairs, 2)
+            length(batch) == 8 && break
+            (pairs[1, k] in busy || pairs[2, k] in busy) && continue
+            push!(batch, pairs[:, k]); push!(busy, pairs[1, k], pairs[2, k])
+        end
+        new_index = merge_landmarks!(a, reduce(hcat, batch); Rc = Rc)
+        cur = new_index[cur]
+    end
+    Int(first[]), cur
 end
 
 "feature_ellipses(x, cov) of the browser monitor (sim/browser/wsserver.jl:72-85): 5 x N [cx; cy; rx; ry; phi], on the device."

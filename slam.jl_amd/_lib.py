@@ -205,6 +205,42 @@ def frame_lib():
     return fl
 
 
+# ---- the second companion library: map joining (include/slamhip_join.h) ------------------------------------------------------
+# Same arrangement as the frame change: libslamhip_join.so links against libslamhip.so (run path $ORIGIN), works on its handles
+# and is opened at the first join, not at import.
+JOIN_LIB_PATH = os.path.join(_HERE, "libslamhip_join.so")
+
+#: every symbol include/slamhip_join.h declares
+JOIN_SIGNATURES = {
+    "slam_ekf_join": (C.c_int, [_h, _h, _ip]),
+}
+
+_join = None
+
+
+def join_lib():
+    """libslamhip_join.so, opened on first use.  No fallback: missing or unloadable is an ImportError.  Refuses SLAMHIP_LIBRARY
+    for the reason frame_lib() gives: the handles would belong to another library than the one the companion is linked against."""
+    global _join
+    if _join is not None:
+        return _join
+    if os.path.abspath(LIB_PATH) != os.path.join(_HERE, "libslamhip.so"):
+        raise ImportError(f"libslamhip_join.so is linked against {os.path.join(_HERE, 'libslamhip.so')}; the handles of "
+                          f"{LIB_PATH} (SLAMHIP_LIBRARY) cannot be passed to it")
+    if not os.path.exists(JOIN_LIB_PATH):
+        raise ImportError(f"{JOIN_LIB_PATH} is missing: build it with `make -C slam.jl_amd/csrc`.  slam.jl_amd has no CPU fallback.")
+    try:
+        jl = C.CDLL(JOIN_LIB_PATH)
+    except OSError as e:  # pragma: no cover - depends on the machine
+        raise ImportError(f"cannot load {JOIN_LIB_PATH}: {e}.  slam.jl_amd has no CPU fallback.") from e
+    for name, (res, args) in JOIN_SIGNATURES.items():
+        fn = getattr(jl, name)
+        fn.restype = res
+        fn.argtypes = args
+    _join = jl
+    return jl
+
+
 def last_error() -> str:
     msg = lib.slam_last_error()
     return msg.decode("utf-8", "replace") if msg else ""

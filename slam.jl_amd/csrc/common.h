@@ -158,7 +158,7 @@ struct slam_ekf {
                          // workgroups, ceil(N / 64), can never overflow (launch_gate refuses a smaller one)
 
     // small device scratch + pinned mirror for scalar outputs
-    double* d_small;     // 64 doubles: [0..11] small results, [40..55] debug stamps, [56] the ready word factor_w1_kernel's workgroups meet on
+    double* d_small;     // 64 doubles: [0..11] small results, [16..17] c and s of a join (ekf_join.hip), [40..55] debug stamps, [56] the ready word factor_w1_kernel's workgroups meet on
     double* h_small;     // pinned, 64 doubles
     int32_t* d_status;   // [4]  [0] = not-PD flag of the last update
     int32_t* h_status;   // pinned

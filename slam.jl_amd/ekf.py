@@ -218,6 +218,7 @@ class EKFSlamState(SlamState):
             max_landmarks = max(64, 2 * N)
         self.np_dtype = npdt
         self.max_landmarks = int(max_landmarks)
+        self.device = int(device)
         self._h = C.c_void_p()
         check(lib.slam_ekf_create(C.byref(self._h), code, self.max_landmarks, int(device)))
         try:
@@ -466,6 +467,43 @@ class EKFSlamState(SlamState):
         R(theta) p + (tx, ty), the heading mpi_to_pi(phi + theta), cov becomes T cov T' with T = blockdiag(R, 1, R, R, ...).
         Enqueued on the state's stream; nothing is downloaded."""
         check(_lib.frame_lib().slam_ekf_transform(self._h, float(tx), float(ty), float(theta)))
+
+    def submap(self, max_landmarks):
+        """A fresh local map for :meth:`join`: a state of the same dtype on the same device with pose (0, 0, 0), no landmark
+        and cov = 0 -- its frame is this state's vehicle pose for as long as this state neither moves nor observes."""
+        return EKFSlamState(np.zeros(3), np.zeros((3, 3)), dtype=self.np_dtype, max_landmarks=int(max_landmarks),
+                            device=self.device)
+
+    def join(self, other, merge_gate=None, Rc=None):
+        """Map joining on the device (slam_ekf_join): the local map ``other``, whose frame is this state's vehicle pose (see
+        :meth:`submap`), is appended to this one: the vehicle is composed with ``other``'s, ``other``'s landmark j becomes landmark
+        N + j, cov becomes F cov F' + G cov_other G'.  ``other`` is only read and may be closed right away.  Returns
+        ``first_new``, the 1-based id of ``other``'s first landmark in this map.
+        With ``merge_gate`` set the overlap is fused afterwards: find_duplicates(merge_gate), then merge_landmarks(.., Rc) on at
+        most SLAM_MERGE_MAX disjoint pairs, round after round until no pair is found; returns ``(first_new, new_index)`` with
+        new_index (int32, one entry per landmark of the joined map) composed over the rounds."""
+        if not isinstance(other, EKFSlamState):
+            raise TypeError("join needs another EKFSlamState")
+        first = C.c_int32()
+        check(_lib.join_lib().slam_ekf_join(self._h, other._h, C.byref(first)))
+        if merge_gate is None:
+            return first.value
+        cur = np.arange(1, self.N + 1, dtype=np.int64)
+        while True:
+            pairs, count = self.find_duplicates(float(merge_gate))
+            if count == 0:
+                break
+            batch, busy = [], set()
+            for a, b in pairs:
+                if len(batch) == _lib.SLAM_MERGE_MAX:
+                    break
+                if int(a) in busy or int(b) in busy:
+                    continue
+                batch.append((int(a), int(b)))
+                busy.update((int(a), int(b)))
+            new_index = np.asarray(self.merge_landmarks(np.asarray(batch, dtype=np.int32), Rc), dtype=np.int64)
+            cur = new_index[cur - 1]
+        return first.value, cur.astype(np.int32)
 
     def align(self, ids, xy, apply=True):
         """Fit the rigid transform (no scale) that carries the means of the landmarks ``ids`` (1-based) onto the surveyed

@@ -140,6 +140,7 @@ class SimLog:
     assoc: list = field(default_factory=list)           # (idf list, n_new) per observation step
     pruned: list = field(default_factory=list)          # (observation step, removed ids) per removal (sim(prune_after=k))
     merged: list = field(default_factory=list)          # (observation step, pairs) per merge (sim(merge_gate=g))
+    joined: list = field(default_factory=list)          # (observation step, first_new, landmarks joined, landmarks after) per join (sim(submap_steps=k))
     true_track: list = field(default_factory=list)
     slam_track: list = field(default_factory=list)
 
@@ -163,7 +164,8 @@ def default_QR():
 
 
 def sim(filt, waypoints: np.ndarray, landmarks: np.ndarray, seed: int, nlaps: int = 2,
-        max_steps: int = 100000, monitor=None, fused: bool = False, prune_after=None, merge_gate=None) -> SimLog:
+        max_steps: int = 100000, monitor=None, fused: bool = False, prune_after=None, merge_gate=None,
+        submap_steps=None) -> SimLog:
     """The loop of sim/ekfslam-sim.jl:80-141 without sleep/pause.
 
     ``filt`` must already hold the initial state (x = initial pose, P = 0).
@@ -178,7 +180,17 @@ def sim(filt, waypoints: np.ndarray, landmarks: np.ndarray, seed: int, nlaps: in
     step ``filt.find_duplicates(g) -> (pairs, count)`` looks for landmarks entered twice and ``filt.merge_landmarks(pairs) ->
     new_index`` fuses them; the ``prune_after`` counters follow ``new_index`` (a merged landmark keeps the earlier birth and
     the larger match count).  Merges are recorded in ``log.merged``.
+    ``submap_steps``: None (default) is the loop above.  An integer k (map joining, no counterpart in the reference): ``filt`` is
+    the GLOBAL map and stays frozen while a local map ``filt.submap(filt.max_landmarks)`` -- pose 0, P = 0, its frame the global
+    vehicle pose -- takes every predict and observation; after k observation steps (and once more when the course ends) it is
+    joined with ``filt.join(local, merge_gate=merge_gate)``, closed, and a new one starts.  With ``merge_gate`` the join fuses the
+    landmarks both maps hold (there is no per-step merge in this mode; ``prune_after`` is refused).  Joins are recorded in
+    ``log.joined``; ``log.slam_track`` holds the local pose composed with the frozen global one.
     """
+    if submap_steps is not None:
+        if prune_after is not None:
+            raise ValueError("prune_after counts matches in one map: not available with submap_steps")
+        return _sim_submaps(filt, waypoints, landmarks, seed, nlaps, max_steps, monitor, fused, merge_gate, int(submap_steps))
     rng = np.random.default_rng(seed)
     Q, R = default_QR()
     vehicle = Vehicle(pose=initial_pose(waypoints))
@@ -241,4 +253,76 @@ def sim(filt, waypoints: np.ndarray, landmarks: np.ndarray, seed: int, nlaps: in
         log.slam_track.append(np.array(filt.pose()))
         if monitor is not None:
             monitor(vehicle, filt, nsteps)
+    return log
+
+
+def _compose(base, local):
+    """The local pose in the frame of ``base``."""
+    c, s_ = math.cos(base[2]), math.sin(base[2])
+    return np.array([base[0] + c * local[0] - s_ * local[1], base[1] + s_ * local[0] + c * local[1],
+                     mpi_to_pi(base[2] + local[2])])
+
+
+def _sim_submaps(glob, waypoints, landmarks, seed, nlaps, max_steps, monitor, fused, merge_gate, k) -> SimLog:
+    """sim(..., submap_steps=k): the same vehicle, sensor and draw order as the plain loop; the filter calls go to a local map."""
+    if k < 1:
+        raise ValueError("submap_steps must be at least 1")
+    rng = np.random.default_rng(seed)
+    Q, R = default_QR()
+    vehicle = Vehicle(pose=initial_pose(waypoints))
+    log = SimLog()
+    dtsum = 0.0
+    nsteps = 0
+    base = np.array(glob.pose(), dtype=float)
+    local = glob.submap(glob.max_landmarks)
+    in_local = 0
+
+    def close_local():
+        nonlocal local, base, in_local
+        nb = int(local.N)
+        out = glob.join(local, merge_gate=merge_gate)
+        first = int(out[0]) if merge_gate is not None else int(out)
+        local.close()
+        log.joined.append((len(log.obs_steps) - 1, first, nb, int(glob.N)))
+        base = np.array(glob.pose(), dtype=float)
+        in_local = 0
+
+    try:
+        while vehicle.waypoint_id != 0 and nsteps < max_steps:
+            steer(vehicle, waypoints, D_MIN, DT)
+            if vehicle.waypoint_id == 0 and nlaps > 1:
+                vehicle.waypoint_id = 1
+                nlaps -= 1
+            step_vehicle(vehicle, DT)
+            vehicle.measured_speed = vehicle.target_speed + rng.standard_normal() * math.sqrt(Q[0, 0])
+            vehicle.measured_gamma = vehicle.target_gamma + rng.standard_normal() * math.sqrt(Q[1, 1])
+            local.predict(vehicle.measured_speed, vehicle.measured_gamma, vehicle.wheelbase, Q, DT)
+            log.controls.append((vehicle.measured_speed, vehicle.measured_gamma))
+            dtsum += DT
+            if dtsum > DT_OBS:
+                dtsum = 0.0
+                z, _tags = get_observations(vehicle, landmarks, R, rng)
+                if fused:
+                    assoc = np.asarray(local.observe(z, R, GATE1, GATE2))
+                    idf = assoc[assoc > 0]
+                    zn = np.asarray(z, dtype=float).reshape(2, -1)[:, assoc < 0]
+                else:
+                    zf, idf, zn = local.associate(z, R, GATE1, GATE2)
+                    local.update(zf, R, idf)
+                    local.add_features(zn, R)
+                log.obs_steps.append(nsteps)
+                log.observations.append(np.array(z))
+                log.assoc.append((np.asarray(idf).reshape(-1).tolist(), int(np.asarray(zn).reshape(2, -1).shape[1])))
+                in_local += 1
+                if in_local == k:
+                    close_local()
+                    local = glob.submap(glob.max_landmarks)
+            nsteps += 1
+            log.true_track.append(np.array(vehicle.pose))
+            log.slam_track.append(_compose(base, np.asarray(local.pose(), dtype=float)))
+            if monitor is not None:
+                monitor(vehicle, glob, nsteps)
+        close_local()                                                     # what the last local map holds, the pose included
+    finally:
+        local.close()
     return log
