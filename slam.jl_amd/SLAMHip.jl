@@ -15,7 +15,7 @@ module SLAMHip
 export SlamState, EKFSlamState, set_state!, predict, update, add_features, associate,
        compute_association, predict_observation, mpi_to_pi,
        ekf_predict!, ekf_update!, augment!, observe!, cov_block, cov_diag, landmark_blocks, gate_mode!, gate_info, state_written!, remove_features!, find_duplicates, merge_landmarks!, transform!, join!, submap, feature_ellipses, vehicle_ellipse,
-       PFSlamState, set_pose!, init_landmarks!, pf_predict!, update_known!, step!, step_async!, step_async_batch!, step_unknown!, flush!,
+       PFSlamState, set_pose!, init_landmarks!, pf_predict!, update_known!, step!, step_async!, step_async_batch!, step_unknown!, LandmarkEvidence, evidence_update!, counters, step_unknown_pruned!, flush!,
        resample!, mean_pose, weights, particles, pf_map, pf_best_particle, peer_blob, attach_peers!, peer_selftest, detach_peers!, comm_info
 
 const libslamhip = get(ENV, "SLAMHIP_LIB", joinpath(@__DIR__, "libslamhip.so"))
@@ -25,6 +25,9 @@ const libslamhip = get(ENV, "SLAMHIP_LIB", joinpath(@__DIR__, "libslamhip.so"))
 const libslamhip_frame = get(ENV, "SLAMHIP_FRAME_LIB", joinpath(@__DIR__, "libslamhip_frame.so"))
 # the companion library of include/slamhip_join.h (map joining), same arrangement (opened at the first join!)
 const libslamhip_join = get(ENV, "SLAMHIP_JOIN_LIB", joinpath(@__DIR__, "libslamhip_join.so"))
+# the companion library of include/slamhip_evidence.h (landmark evidence and pruning of the unknown-correspondence particle
+# filter), same arrangement (opened at the first LandmarkEvidence)
+const libslamhip_evidence = get(ENV, "SLAMHIP_EVIDENCE_LIB", joinpath(@__DIR__, "libslamhip_evidence.so"))
 
 const SLAM_OK = Cint(0)
 const SLAM_PF_HALTED = Cint(1)
@@ -515,6 +518,100 @@ function step_unknown!(s::PFSlamState, V::Real, G::Real, wheelbase::Real, Q::Abs
                 s.handle, V, G, wheelbase, colmajor4(Q), dt, pairs64(z), size(z, 2), colmajor4(R), gate1, gate2,
                 Ptr{Int32}(C_NULL), out))
     out
+end
+
+"""
+    LandmarkEvidence(state, r_max, half_fov; inc = 1, dec = 1, init = 1, cap = 5)
+
+Landmark evidence of an unknown-correspondence filter (include/slamhip_evidence.h): one Int8 existence counter per (slot,
+particle) on the device, raised by `inc` (up to `cap`) when the step matched the slot, lowered by `dec` when the landmark lies
+within `r_max` and +-`half_fov` of the particle's pose and was not observed; below zero the record is discarded.  Only a filter
+that lives wholly on one rank (`world == 1`).  The object borrows `state` (kept alive through the field) and must be the only
+way the filter is resampled: `step_unknown_pruned!` does that.
+"""
+mutable struct LandmarkEvidence
+    handle::Ptr{Cvoid}
+    state::PFSlamState
+    r_max::Float64
+    half_fov::Float64
+    inc::Int
+    dec::Int
+    init::Int
+    cap::Int
+    resamples::Int
+    function LandmarkEvidence(s::PFSlamState, r_max::Real, half_fov::Real; inc::Integer = 1, dec::Integer = 1, init::Integer = 1,
+                              cap::Integer = 5)
+        s.world == 1 || error("landmark evidence supports only a filter that lives wholly on one rank")
+        h = Ref{Ptr{Cvoid}}(C_NULL)
+        check(ccall((:slam_pf_evidence_create, libslamhip_evidence), Cint, (Ref{Ptr{Cvoid}}, Ptr{Cvoid}), h, s.handle))
+        e = new(h[], s, r_max, half_fov, inc, dec, init, cap, 0)
+        finalizer(e) do ev
+            ccall((:slam_pf_evidence_destroy, libslamhip_evidence), Cint, (Ptr{Cvoid},), ev.handle)
+        end
+        return e
+    end
+end
+
+"One pass of the rule with the DEVICE array `d_assoc` ([m][n] Int32) of the step just made: [in use, created, decremented, pruned]."
+function evidence_update!(e::LandmarkEvidence, d_assoc::Ptr{Int32}, m::Integer)
+    counts = zeros(Int64, 4)
+    check(ccall((:slam_pf_evidence_update, libslamhip_evidence), Cint,
+                (Ptr{Cvoid}, Ptr{Int32}, Cint, Cdouble, Cdouble, Cint, Cint, Cint, Cint, Ptr{Int64}),
+                e.handle, d_assoc, m, e.r_max, e.half_fov, e.inc, e.dec, e.init, e.cap, counts))
+    counts
+end
+
+"The counters, `max_landmarks x n` Int8 (-128: no landmark in that slot of that particle)."
+function counters(e::LandmarkEvidence)
+    out = zeros(Int8, e.state.n, e.state.max_landmarks)          # the library's [nl][n], particle index fastest
+    check(ccall((:slam_pf_evidence_get, libslamhip_evidence), Cint, (Ptr{Cvoid}, Ptr{Int8}), e.handle, out))
+    permutedims(out)
+end
+
+# One U(0,1) from Philox4x32-10 with counter (0, 0, step, stream): the systematic-resampling offset (pf.py: philox_uniform)
+function philox_uniform(step::Integer, stream::Integer, seed::Integer)
+    c = UInt32[0, 0, step % UInt32, stream % UInt32]
+    k0, k1 = UInt32(seed & 0xffffffff), UInt32((seed >> 32) & 0xffffffff)
+    for _ in 1:10
+        p0, p1 = UInt64(0xD2511F53) * c[1], UInt64(0xCD9E8D57) * c[3]
+        c = UInt32[(p1 >> 32) % UInt32 ⊻ c[2] ⊻ k0, p1 % UInt32, (p0 >> 32) % UInt32 ⊻ c[4] ⊻ k1, p0 % UInt32]
+        k0 += 0x9E3779B9
+        k1 += 0xBB67AE85
+    end
+    ((c[1] >> 8) + 0.5) / 16777216.0
+end
+
+"""
+    step_unknown_pruned!(state, evidence, V, G, wheelbase, Q, dt, z, R, gate1, gate2; neff_frac = 0.75, seed = 0)
+        -> (Neff, resampled, counts)
+
+`step_unknown!` with landmark evidence (slam_pf_step_unknown_evidence), the normalisation, and -- if Neff < neff_frac * n --
+systematic resampling through slam_pf_evidence_resample, so that the counters follow their particles.  `seed`: the filter's seed
+(it keys the resampling offset).  `counts` = [records in use, created, decremented, pruned] of this step.
+"""
+function step_unknown_pruned!(s::PFSlamState{T}, e::LandmarkEvidence, V::Real, G::Real, wheelbase::Real, Q::AbstractMatrix, dt::Real,
+                              z::AbstractMatrix, R::AbstractMatrix, gate1::Real, gate2::Real; neff_frac::Real = 0.75,
+                              seed::Integer = 0) where {T}
+    e.state === s || error("the evidence object belongs to another filter")
+    out = zeros(Float64, 3)
+    counts = zeros(Int64, 4)
+    check(ccall((:slam_pf_step_unknown_evidence, libslamhip_evidence), Cint,
+                (Ptr{Cvoid}, Cdouble, Cdouble, Cdouble, Ptr{Cdouble}, Cdouble, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cdouble, Cdouble,
+                 Cdouble, Cdouble, Cint, Cint, Cint, Cint, Ptr{Cdouble}, Ptr{Int64}),
+                e.handle, V, G, wheelbase, colmajor4(Q), dt, pairs64(z), size(z, 2), colmajor4(R), gate1, gate2,
+                e.r_max, e.half_fov, e.inc, e.dec, e.init, e.cap, out, counts))
+    gmax, s1, s2 = out
+    check(ccall((:slam_pf_normalize, libslamhip), Cint, (Ptr{Cvoid}, Cdouble, Cdouble), s.handle, gmax, s1))
+    neff = s1 * s1 / s2
+    did = neff < neff_frac * s.n
+    if did
+        gnorm = Float64(T(gmax) - T(gmax + log(s1)))      # the largest log-weight after the shift, as stored
+        check(ccall((:slam_pf_evidence_resample, libslamhip_evidence), Cint, (Ptr{Cvoid}, Cdouble, Cdouble),
+                    e.handle, gnorm, philox_uniform(e.resamples, 2, seed)))
+        e.resamples += 1
+        check(ccall((:slam_pf_set_resample_count, libslamhip), Cint, (Ptr{Cvoid}, Int64), s.handle, e.resamples))
+    end
+    neff, did, counts
 end
 
 """

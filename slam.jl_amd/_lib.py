@@ -241,6 +241,54 @@ def join_lib():
     return jl
 
 
+# ---- the third companion library: landmark evidence and pruning (include/slamhip_evidence.h) --------------------------------
+# Same arrangement again: libslamhip_evidence.so links against libslamhip.so (run path $ORIGIN), works on its particle-filter
+# handles and is opened when the first evidence object is made, not at import.
+EVIDENCE_LIB_PATH = os.path.join(_HERE, "libslamhip_evidence.so")
+SLAM_PF_EVIDENCE_EMPTY = -128
+SLAM_PF_EVIDENCE_MAXOBS = 64
+_i64p = C.POINTER(C.c_int64)
+
+#: every symbol include/slamhip_evidence.h declares
+EVIDENCE_SIGNATURES = {
+    "slam_pf_evidence_create": (C.c_int, [C.POINTER(_h), _h]),
+    "slam_pf_evidence_destroy": (C.c_int, [_h]),
+    "slam_pf_evidence_update": (C.c_int, [_h, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int,
+                                          _i64p]),
+    "slam_pf_step_unknown_evidence": (C.c_int, [_h, C.c_double, C.c_double, C.c_double, _dp, C.c_double, _dp, C.c_int, _dp,
+                                                C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int,
+                                                C.c_int, _dp, _i64p]),
+    "slam_pf_evidence_resample": (C.c_int, [_h, C.c_double, C.c_double]),
+    "slam_pf_evidence_get": (C.c_int, [_h, C.c_void_p]),
+}
+
+_evidence = None
+
+
+def evidence_lib():
+    """libslamhip_evidence.so, opened on first use.  No fallback: missing or unloadable is an ImportError.  Refuses
+    SLAMHIP_LIBRARY for the reason frame_lib() gives: the handles would belong to another library than the one the companion is
+    linked against."""
+    global _evidence
+    if _evidence is not None:
+        return _evidence
+    if os.path.abspath(LIB_PATH) != os.path.join(_HERE, "libslamhip.so"):
+        raise ImportError(f"libslamhip_evidence.so is linked against {os.path.join(_HERE, 'libslamhip.so')}; the handles of "
+                          f"{LIB_PATH} (SLAMHIP_LIBRARY) cannot be passed to it")
+    if not os.path.exists(EVIDENCE_LIB_PATH):
+        raise ImportError(f"{EVIDENCE_LIB_PATH} is missing: build it with `make -C slam.jl_amd/csrc`.  slam.jl_amd has no CPU fallback.")
+    try:
+        el = C.CDLL(EVIDENCE_LIB_PATH)
+    except OSError as e:  # pragma: no cover - depends on the machine
+        raise ImportError(f"cannot load {EVIDENCE_LIB_PATH}: {e}.  slam.jl_amd has no CPU fallback.") from e
+    for name, (res, args) in EVIDENCE_SIGNATURES.items():
+        fn = getattr(el, name)
+        fn.restype = res
+        fn.argtypes = args
+    _evidence = el
+    return el
+
+
 def last_error() -> str:
     msg = lib.slam_last_error()
     return msg.decode("utf-8", "replace") if msg else ""

@@ -28,10 +28,10 @@ import sys
 
 import numpy as np
 
-from ._lib import SLAM_F32, SLAM_F64, SLAM_PF_HALTED, SLAM_PF_PEER_BLOB_BYTES, check, frame_lib, lib
+from ._lib import SLAM_F32, SLAM_F64, SLAM_PF_HALTED, SLAM_PF_PEER_BLOB_BYTES, check, evidence_lib, frame_lib, lib
 from .ekf import _obs, _small, _ptr, rigid_fit
 
-__all__ = ["PFShard", "PFSlamState", "FastSLAM", "philox_uniform", "small", "shared_page", "attach_local_peers",
+__all__ = ["PFShard", "PFSlamState", "FastSLAM", "LandmarkEvidence", "philox_uniform", "small", "shared_page", "attach_local_peers",
            "finalise_map", "ellipse_axes", "MapSnapshot"]
 
 _M0, _M1, _W0, _W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
@@ -537,6 +537,80 @@ class PFShard:
         check(lib.slam_pf_sync(self._h))
 
 
+class LandmarkEvidence:
+    """Landmark evidence of an unknown-correspondence filter (include/slamhip_evidence.h): one int8 existence counter per
+    (slot, particle) on the device, raised by ``inc`` (up to ``cap``) when the step matched the slot, lowered by ``dec`` when the
+    landmark lies within ``r_max`` and +-``half_fov`` of the particle's pose and was not observed; below zero the record is
+    discarded and its slot is free again.  A record made since the last pass starts at ``init``.
+
+    ``shard`` is a :class:`PFShard` that holds the WHOLE filter (no peers; sharded filters are not supported).  The object
+    borrows the shard: close it before the shard.  A filter with an evidence object is resampled through :meth:`resample`
+    (``FastSLAM.step_unknown_pruned`` does) and through nothing else -- otherwise the counters no longer belong to their
+    particles."""
+    EMPTY = -128
+
+    def __init__(self, shard, r_max, half_fov, inc=1, dec=1, init=1, cap=5):
+        self.shard = shard
+        self.r_max, self.half_fov = float(r_max), float(half_fov)
+        self.inc, self.dec, self.init, self.cap = int(inc), int(dec), int(init), int(cap)
+        self._e = C.c_void_p()
+        self._lib = evidence_lib()
+        check(self._lib.slam_pf_evidence_create(C.byref(self._e), shard._h))
+
+    def close(self):
+        if getattr(self, "_e", None) is not None and self._e:
+            if self.shard._h:                       # (a shard closed first took the stream along: nothing left to free on)
+                self._lib.slam_pf_evidence_destroy(self._e)
+            self._e = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _rule(self):
+        return self.r_max, self.half_fov, self.inc, self.dec, self.init, self.cap
+
+    def update(self, assoc, want_counts=True, assume_ready=False):
+        """One pass of the rule with the decisions ``assoc`` of the step just made: the int32 torch tensor [m, n] on the
+        shard's device that ``update_unknown`` / ``step_unknown_fused`` returned (None: no observation).  Returns the counts
+        [records in use, created, decremented, pruned] as int64 (the call then synchronises), or None.  ``assume_ready``: the
+        tensor is known to be complete (it came from a call that synchronises), so the device is not synchronised first."""
+        m, ptr = 0, None
+        if assoc is not None and assoc.numel():
+            import torch
+            assert assoc.is_cuda and assoc.dtype == torch.int32 and assoc.is_contiguous() and assoc.shape[1] == self.shard.n
+            if not assume_ready:
+                torch.cuda.synchronize(self.shard.device)    # assoc may have been produced on torch's stream
+            m, ptr = int(assoc.shape[0]), C.c_void_p(assoc.data_ptr())
+        counts = np.zeros(4, dtype=np.int64) if want_counts else None
+        check(self._lib.slam_pf_evidence_update(self._e, ptr, m, *self._rule(), _ptr(counts, C.c_int64) if want_counts else None))
+        return counts
+
+    def step(self, V, G, wheelbase, Q, dt, z, R, gate1, gate2, want_counts=True):
+        """``PFShard.step_unknown_fused`` followed by :meth:`update` with its decisions, as one library call
+        (slam_pf_step_unknown_evidence).  Returns ((gmax, s1, s2), counts)."""
+        zp = _obs(z)
+        q, r = _small(Q), _small(R)
+        out = np.empty(3)
+        counts = np.zeros(4, dtype=np.int64) if want_counts else None
+        check(self._lib.slam_pf_step_unknown_evidence(self._e, float(V), float(G), float(wheelbase), _ptr(q), float(dt), _ptr(zp),
+                                                      zp.shape[0], _ptr(r), float(gate1), float(gate2), *self._rule(), _ptr(out),
+                                                      _ptr(counts, C.c_int64) if want_counts else None))
+        return (float(out[0]), float(out[1]), float(out[2])), counts
+
+    def resample(self, gmax, u0):
+        """``PFShard.resample_local`` with the counters following their particles (slam_pf_evidence_resample)."""
+        check(self._lib.slam_pf_evidence_resample(self._e, float(gmax), float(u0)))
+
+    def counters(self):
+        """The counters, int8 [nl, n] (EMPTY = -128: no landmark in that slot of that particle)."""
+        out = np.empty((self.shard.nl, self.shard.n), dtype=np.int8)
+        check(self._lib.slam_pf_evidence_get(self._e, out.ctypes.data))
+        return out
+
+
 class _SingleProcess:
     """The world of one rank."""
     rank, world = 0, 1
@@ -855,6 +929,24 @@ class FastSLAM:
         if do:
             self.resample()
         return neff, bool(do)
+
+    def step_unknown_pruned(self, V, G, wheelbase, Q, dt, z, R, gate1, gate2, evidence, force_resample=None):
+        """``step_unknown_fused`` with landmark evidence: the step is taken through ``evidence.step`` (a
+        :class:`LandmarkEvidence` of this filter's shard: association + updates / new landmarks, then the counters and the
+        pruning), and a resampling goes through ``evidence.resample`` so that the counters follow their particles.  Pruning
+        touches no weight.  Whole filter on one rank only.  Returns (Neff, resampled?, counts) with counts = [records in
+        use, created, decremented, pruned] of this step."""
+        assert self.comm.world == 1, "landmark evidence supports only a filter that lives wholly on one rank"
+        self._gmax_norm = None
+        stats, counts = evidence.step(V, G, wheelbase, Q, dt, z, R, gate1, gate2)
+        neff = self.normalize(stats)
+        do = force_resample if force_resample is not None else (neff < self.neff_frac * self.shard.n_global)
+        if do:
+            u0 = philox_uniform(self.resamples, STREAM_RESAMPLE, self.shard.seed)
+            evidence.resample(self._gmax_norm, u0)
+            self._gmax_norm = None
+            self._count_resampling()
+        return neff, bool(do), counts
 
     def mean_pose(self):
         s = self.comm.allreduce_sum(list(self.shard.mean_pose_sums()))

@@ -115,4 +115,8 @@ end
     out = flush!(pf)
     @test out[4] == 3 && 1 < out[1] <= 4096
     @test all(isfinite, mean_pose(pf))
+    # landmark evidence: the eight records made above receive `init`, the two observed ones are matched at the second step
+    ev = LandmarkEvidence(pf, 30.0, pi / 2)
+    neff, did, counts = step_unknown_pruned!(pf, ev, 1.0, 0.0, 4.0, Q, 0.025, z, R, 4.0, 25.0; seed = 1234)
+    @test counts[1] == 8 * 4096 && counts[2] == 8 * 4096 && counts[4] == 0 && all(counters(ev) .== 1)
 end
