@@ -14,7 +14,7 @@ module SLAMHip
 
 export SlamState, EKFSlamState, set_state!, predict, update, add_features, associate,
        compute_association, predict_observation, mpi_to_pi,
-       ekf_predict!, ekf_update!, augment!, observe!, cov_block, cov_diag, landmark_blocks, gate_mode!, gate_info, state_written!, remove_features!, find_duplicates, merge_landmarks!, transform!, join!, submap, feature_ellipses, vehicle_ellipse,
+       ekf_predict!, ekf_update!, augment!, observe!, cov_block, cov_diag, landmark_blocks, gate_mode!, gate_info, state_written!, remove_features!, find_duplicates, merge_landmarks!, transform!, join!, submap, associate_joint, observe_joint!, joint_nis, chi2_table, feature_ellipses, vehicle_ellipse,
        PFSlamState, set_pose!, init_landmarks!, pf_predict!, update_known!, step!, step_async!, step_async_batch!, step_unknown!, LandmarkEvidence, evidence_update!, counters, step_unknown_pruned!, flush!,
        resample!, mean_pose, weights, particles, pf_map, pf_best_particle, peer_blob, attach_peers!, peer_selftest, detach_peers!, comm_info
 
@@ -28,6 +28,9 @@ const libslamhip_join = get(ENV, "SLAMHIP_JOIN_LIB", joinpath(@__DIR__, "libslam
 # the companion library of include/slamhip_evidence.h (landmark evidence and pruning of the unknown-correspondence particle
 # filter), same arrangement (opened at the first LandmarkEvidence)
 const libslamhip_evidence = get(ENV, "SLAMHIP_EVIDENCE_LIB", joinpath(@__DIR__, "libslamhip_evidence.so"))
+# the companion library of include/slamhip_jc.h (joint-compatibility data association for the EKF), same arrangement (opened at the
+# first associate_joint / joint_nis)
+const libslamhip_jc = get(ENV, "SLAMHIP_JC_LIB", joinpath(@__DIR__, "libslamhip_jc.so"))
 
 const SLAM_OK = Cint(0)
 const SLAM_PF_HALTED = Cint(1)
@@ -58,13 +61,15 @@ new feature, src/ekf.jl:108-109).
 mutable struct EKFSlamState{T<:Union{Float32,Float64}} <: SlamState
     handle::Ptr{Cvoid}
     device::Int                                   # the device the handle lives on (submap creates its local map there)
+    jc::Ptr{Cvoid}                                # the joint-compatibility search workspace (slam_ekf_jc_create), C_NULL until first used
     function EKFSlamState{T}(x::AbstractVector, cov::AbstractMatrix;
                              max_landmarks::Integer = max(64, length(x) - 3), device::Integer = 0) where {T}
         h = Ref{Ptr{Cvoid}}(C_NULL)
         check(ccall((:slam_ekf_create, libslamhip), Cint, (Ref{Ptr{Cvoid}}, Cint, Cint, Cint),
                     h, T === Float32 ? SLAM_F32 : SLAM_F64, max_landmarks, device))
-        s = new{T}(h[], Int(device))
+        s = new{T}(h[], Int(device), C_NULL)
         finalizer(s) do st
+            getfield(st, :jc) == C_NULL || ccall((:slam_ekf_jc_destroy, libslamhip_jc), Cint, (Ptr{Cvoid},), getfield(st, :jc))   # it borrows the handle: first
             ccall((:slam_ekf_destroy, libslamhip), Cint, (Ptr{Cvoid},), getfield(st, :handle))
         end
         set_state!(s, x, cov)
@@ -380,6 +385,97 @@ function associate(s::EKFSlamState, z::AbstractMatrix, R::AbstractMatrix, gate1:
     hit = findall(>(0), assoc)
     new = findall(<(0), assoc)
     z[:, hit], reshape(Int.(assoc[hit]), 1, :), z[:, new]
+end
+
+# ---- joint-compatibility data association (include/slamhip_jc.h; no counterpart in the reference) -------------------------------
+"""
+    chi2_table(m, confidence = 0.95)
+
+Thresholds of the joint-compatibility search: entry k is the chi-square quantile at `confidence` with 2k degrees of freedom, from the
+closed form for even degrees of freedom, 1 - exp(-x/2) sum_{i<k} (x/2)^i / i!, by bisection.
+"""
+function chi2_table(m::Integer, confidence::Real = 0.95)
+    0 < confidence < 1 || error("confidence must lie strictly between 0 and 1")
+    function cdf(x, k)
+        h, term, acc = x / 2, 1.0, 0.0
+        for i in 0:k-1
+            acc += term
+            term *= h / (i + 1)
+        end
+        1 - exp(-h) * acc
+    end
+    out = zeros(Float64, m)
+    for k in 1:m
+        lo, hi = 0.0, 4.0 * k + 16.0
+        while cdf(hi, k) < confidence
+            hi *= 2
+        end
+        for _ in 1:200
+            mid = (lo + hi) / 2
+            (mid == lo || mid == hi) && break
+            cdf(mid, k) < confidence ? (lo = mid) : (hi = mid)
+        end
+        out[k] = (lo + hi) / 2
+    end
+    out
+end
+
+function jc_handle(s::EKFSlamState)
+    if getfield(s, :jc) == C_NULL
+        h = Ref{Ptr{Cvoid}}(C_NULL)
+        check(ccall((:slam_ekf_jc_create, libslamhip_jc), Cint, (Ref{Ptr{Cvoid}}, Ptr{Cvoid}), h, handle(s)))
+        setfield!(s, :jc, h[])
+    end
+    getfield(s, :jc)
+end
+
+"The association vector (j >= 1 matched, 0 dropped, -1 new) and the info record of slam_ekf_associate_joint."
+function associate_joint_vector(s::EKFSlamState, z::AbstractMatrix, R::AbstractMatrix, gate1::Real, gate2::Real;
+                                confidence::Real = 0.95, max_nodes::Integer = 20000)
+    nz = size(z, 2)
+    assoc = zeros(Int32, nz)
+    info = zeros(Float64, 8)
+    chi2 = chi2_table(max(nz, 1), confidence)
+    check(ccall((:slam_ekf_associate_joint, libslamhip_jc), Cint,
+                (Ptr{Cvoid}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cdouble, Cdouble, Ptr{Cdouble}, Int64, Ptr{Int32}, Ptr{Cdouble}),
+                jc_handle(s), pairs64(z), nz, colmajor4(R), gate1, gate2, chi2, max_nodes, assoc, info))
+    assoc, (pairings = Int(info[1]), d2 = info[2], tests = Int(info[3]), exhausted = info[4] != 0, truncated = info[5] != 0,
+            candidates = Int(info[6]), deepest = Int(info[7]))
+end
+
+"""
+    associate_joint(state, z, R, gate1, gate2; confidence = 0.95, max_nodes = 20000) -> (zf, idf, zn, info)
+
+`associate` with the decisions of the joint-compatibility search: the largest set of pairings, each landmark used at most once, whose
+stacked innovation passes the chi-square test against the joint innovation covariance (at most 64 observations).  The state is not
+changed.
+"""
+function associate_joint(s::EKFSlamState, z::AbstractMatrix, R::AbstractMatrix, gate1::Real, gate2::Real; kw...)
+    assoc, info = associate_joint_vector(s, z, R, gate1, gate2; kw...)
+    hit = findall(>(0), assoc)
+    new = findall(<(0), assoc)
+    z[:, hit], reshape(Int.(assoc[hit]), 1, :), z[:, new], info
+end
+
+"associate_joint, then ekf_update!, then augment!  -> (association vector, info)."
+function observe_joint!(s::EKFSlamState, z::AbstractMatrix, R::AbstractMatrix, gate1::Real, gate2::Real;
+                        form::Symbol = :cholesky, kw...)
+    assoc, info = associate_joint_vector(s, z, R, gate1, gate2; kw...)
+    hit = findall(>(0), assoc)
+    new = findall(<(0), assoc)
+    isempty(hit) || ekf_update!(s, z[:, hit], R, Int.(assoc[hit]); form = form)
+    isempty(new) || augment!(s, z[:, new], R)
+    assoc, info
+end
+
+"d2 = v' inv(S_H) v of the hypothesis observation i <-> landmark idf[i] (1-based, distinct) under the joint covariance (slam_ekf_joint_nis)."
+function joint_nis(s::EKFSlamState, z::AbstractMatrix, idf, R::AbstractMatrix)
+    ids = Int32.(vec(collect(idf)))
+    length(ids) == size(z, 2) || error("idf and z disagree on the number of observations")
+    out = Ref{Cdouble}(0.0)
+    check(ccall((:slam_ekf_joint_nis, libslamhip_jc), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Int32}, Cint, Ptr{Cdouble}, Ref{Cdouble}),
+                jc_handle(s), pairs64(z), ids, length(ids), colmajor4(R), out))
+    out[]
 end
 
 "compute_association(state, z, R, idf) -> (nis, nd)  (src/data-association.jl:53-63; x, P are the state's)."

@@ -289,6 +289,48 @@ def evidence_lib():
     return el
 
 
+# ---- the fourth companion library: joint-compatibility data association (include/slamhip_jc.h) -------------------------------
+# Same arrangement again: libslamhip_jc.so links against libslamhip.so (run path $ORIGIN), works on its EKF handles and is
+# opened when the first search workspace is made, not at import.
+JC_LIB_PATH = os.path.join(_HERE, "libslamhip_jc.so")
+SLAM_JC_MAXOBS = 64
+SLAM_JC_MAXCAND = 8
+SLAM_JC_NODE_CAP = 40000
+
+#: every symbol include/slamhip_jc.h declares
+JC_SIGNATURES = {
+    "slam_ekf_jc_create": (C.c_int, [C.POINTER(_h), _h]),
+    "slam_ekf_jc_destroy": (C.c_int, [_h]),
+    "slam_ekf_associate_joint": (C.c_int, [_h, _dp, C.c_int, _dp, C.c_double, C.c_double, _dp, C.c_int64, _ip, _dp]),
+    "slam_ekf_joint_nis": (C.c_int, [_h, _dp, _ip, C.c_int, _dp, _dp]),
+}
+
+_jc = None
+
+
+def jc_lib():
+    """libslamhip_jc.so, opened on first use.  No fallback: missing or unloadable is an ImportError.  Refuses SLAMHIP_LIBRARY
+    for the reason frame_lib() gives: the handles would belong to another library than the one the companion is linked against."""
+    global _jc
+    if _jc is not None:
+        return _jc
+    if os.path.abspath(LIB_PATH) != os.path.join(_HERE, "libslamhip.so"):
+        raise ImportError(f"libslamhip_jc.so is linked against {os.path.join(_HERE, 'libslamhip.so')}; the handles of "
+                          f"{LIB_PATH} (SLAMHIP_LIBRARY) cannot be passed to it")
+    if not os.path.exists(JC_LIB_PATH):
+        raise ImportError(f"{JC_LIB_PATH} is missing: build it with `make -C slam.jl_amd/csrc`.  slam.jl_amd has no CPU fallback.")
+    try:
+        cl = C.CDLL(JC_LIB_PATH)
+    except OSError as e:  # pragma: no cover - depends on the machine
+        raise ImportError(f"cannot load {JC_LIB_PATH}: {e}.  slam.jl_amd has no CPU fallback.") from e
+    for name, (res, args) in JC_SIGNATURES.items():
+        fn = getattr(cl, name)
+        fn.restype = res
+        fn.argtypes = args
+    _jc = cl
+    return cl
+
+
 def last_error() -> str:
     msg = lib.slam_last_error()
     return msg.decode("utf-8", "replace") if msg else ""

@@ -35,6 +35,7 @@ __all__ = [
     "compute_association", "predict_observation", "mpi_to_pi", "ekf_predict_", "ekf_update_", "augment_",
     "remove_features", "remove_features_", "removal_maps",
     "find_duplicates", "merge_features", "merge_features_", "merge_in_batches",
+    "chi2_table", "associate_joint", "observe_joint",
 ]
 
 _DTYPES = {"f32": (SLAM_F32, np.float32), "f64": (SLAM_F64, np.float64),
@@ -165,6 +166,49 @@ def rigid_fit(src, dst):
     return float(cb[0, 0] - (c * ca[0, 0] - s * ca[1, 0])), float(cb[1, 0] - (s * ca[0, 0] + c * ca[1, 0])), theta
 
 
+def chi2_table(m, confidence=0.95):
+    """The thresholds of the joint-compatibility search: entry k - 1 is the chi-square quantile at ``confidence`` with 2k degrees of
+    freedom, k = 1 .. m.  For even degrees of freedom the distribution function has the closed form
+    1 - exp(-x / 2) sum_{i < k} (x / 2)^i / i!; the quantile is found by bisection (no scipy)."""
+    confidence = float(confidence)
+    if not 0.0 < confidence < 1.0:
+        raise ValueError("confidence must lie strictly between 0 and 1")
+    m = int(m)
+    have = _CHI2_CACHE.get(confidence)
+    if have is not None and have.size >= m:
+        return have[:m].copy()
+
+    def cdf(x, k):
+        h, term, acc = 0.5 * x, 1.0, 0.0
+        for i in range(k):
+            acc += term
+            term *= h / (i + 1)
+        return 1.0 - math.exp(-h) * acc
+
+    out = np.empty(int(m))
+    for k in range(1, int(m) + 1):
+        lo, hi = 0.0, 4.0 * k + 16.0
+        while cdf(hi, k) < confidence:
+            hi *= 2.0
+        for _ in range(200):
+            mid = 0.5 * (lo + hi)
+            if mid == lo or mid == hi:
+                break
+            if cdf(mid, k) < confidence:
+                lo = mid
+            else:
+                hi = mid
+        out[k - 1] = 0.5 * (lo + hi)
+    _CHI2_CACHE[confidence] = out.copy()
+    return out
+
+
+_CHI2_CACHE = {}                    # confidence -> the longest table computed so far (a filter asks for the same one every step)
+
+
+JC_INFO_KEYS = ("pairings", "d2", "tests", "exhausted", "truncated", "candidates", "deepest")
+
+
 class SlamState:
     """``abstract SlamState`` (src/common.jl:22)."""
 
@@ -229,6 +273,9 @@ class EKFSlamState(SlamState):
 
     # -- lifetime ----------------------------------------------------------------
     def close(self):
+        if getattr(self, "_jc", None):
+            _lib.jc_lib().slam_ekf_jc_destroy(self._jc)               # the search workspace borrows the handle: it goes first
+            self._jc = None
         if getattr(self, "_h", None) is not None and self._h:
             lib.slam_ekf_destroy(self._h)
             self._h = C.c_void_p()
@@ -534,6 +581,65 @@ class EKFSlamState(SlamState):
                                        _ptr(assoc, C.c_int32)))
         return assoc
 
+    # -- joint-compatibility data association (include/slamhip_jc.h) ---------------------------
+    def _jc_handle(self):
+        """The search workspace (slam_ekf_jc_create), made at the first joint call and destroyed by close()."""
+        if getattr(self, "_jc", None) is None:
+            jc = C.c_void_p()
+            check(_lib.jc_lib().slam_ekf_jc_create(C.byref(jc), self._h))
+            self._jc = jc
+        return self._jc
+
+    def associate_joint_vector(self, z, R, gate1, gate2, confidence=0.95, max_nodes=20000, chi2=None):
+        """(assoc, info): the association vector of associate_vector (j >= 1 matched, 0 dropped, -1 new) from the
+        joint-compatibility search (slam_ekf_associate_joint: at most 64 observations, each landmark used at most once, the stacked
+        innovation of the result inside the chi-square gate of ``confidence``), and ``info``: pairings, d2, tests, exhausted,
+        truncated, candidates, deepest.  ``chi2`` overrides the thresholds of chi2_table(nz, confidence).  The state is not changed."""
+        zp = _obs(z)
+        nz = zp.shape[0]
+        assoc = np.zeros(nz, dtype=np.int32)
+        info = np.zeros(8)
+        table = np.ascontiguousarray(chi2_table(nz, confidence) if chi2 is None else np.asarray(chi2, dtype=np.float64))
+        if table.size < nz:
+            raise ValueError("chi2 needs one threshold per observation")
+        r = _small(R)
+        check(_lib.jc_lib().slam_ekf_associate_joint(self._jc_handle(), _ptr(zp) if nz else None, nz, _ptr(r), float(gate1),
+                                                     float(gate2), _ptr(table) if nz else None, int(max_nodes),
+                                                     _ptr(assoc, C.c_int32) if nz else None, _ptr(info)))
+        d = dict(zip(JC_INFO_KEYS, (float(v) for v in info[:7])))
+        for key in JC_INFO_KEYS:
+            if key != "d2":
+                d[key] = int(d[key])
+        return assoc, d
+
+    def associate_joint(self, z, R, gate1, gate2, confidence=0.95, max_nodes=20000):
+        """(zf, idf, zn, info) in associate()'s shapes, from the joint-compatibility search (associate_joint_vector)."""
+        z = np.asarray(z, dtype=np.float64).reshape(2, -1)
+        assoc, info = self.associate_joint_vector(z, R, gate1, gate2, confidence, max_nodes)
+        return z[:, assoc > 0], assoc[assoc > 0].astype(np.int64).reshape(1, -1), z[:, assoc < 0], info
+
+    def joint_nis(self, z, idf, R):
+        """d2 = v' inv(S_H) v of the hypothesis "observation i is landmark idf[i]" (1-based, distinct) under the JOINT innovation
+        covariance H P H' + blockdiag(R) (slam_ekf_joint_nis).  NotPositiveDefinite if that matrix has a pivot that is not positive."""
+        zp = _obs(z)
+        ids = np.ascontiguousarray(np.asarray(idf, dtype=np.int32).reshape(-1))
+        if ids.shape[0] != zp.shape[0]:
+            raise ValueError("idf and z disagree on the number of observations")
+        r = _small(R)
+        out = C.c_double()
+        check(_lib.jc_lib().slam_ekf_joint_nis(self._jc_handle(), _ptr(zp), _ptr(ids, C.c_int32), int(ids.shape[0]), _ptr(r),
+                                               C.byref(out)))
+        return out.value
+
+    def observe_joint(self, z, R, gate1, gate2, confidence=0.95, max_nodes=20000, form="cholesky"):
+        """associate_joint -> update -> add_features.  Returns ``(assoc, info)``; the state afterwards equals the three calls made
+        by hand."""
+        z = np.asarray(z, dtype=np.float64).reshape(2, -1)
+        assoc, info = self.associate_joint_vector(z, R, gate1, gate2, confidence, max_nodes)
+        self.update(z[:, assoc > 0], R, assoc[assoc > 0], form=form)
+        self.add_features(z[:, assoc < 0], R)
+        return assoc, info
+
     def compute_association(self, z, R, idf):
         zz = _dbl(z, 2)
         r = _small(R)
@@ -650,6 +756,16 @@ def associate(state: SlamState, z, R, gate1, gate2):
 def observe(state: EKFSlamState, z, R, gate1, gate2, form="cholesky"):
     """associate + update + add_features (sim/ekfslam-sim.jl:114-120) in one call -> association vector."""
     return _state_of(state).observe(z, R, gate1, gate2, form=form)
+
+
+def associate_joint(state: EKFSlamState, z, R, gate1, gate2, confidence=0.95, max_nodes=20000):
+    """Joint-compatibility association -> (zf, idf, zn, info) (see EKFSlamState.associate_joint)."""
+    return _state_of(state).associate_joint(z, R, gate1, gate2, confidence, max_nodes)
+
+
+def observe_joint(state: EKFSlamState, z, R, gate1, gate2, confidence=0.95, max_nodes=20000, form="cholesky"):
+    """associate_joint + update + add_features -> (association vector, info)."""
+    return _state_of(state).observe_joint(z, R, gate1, gate2, confidence, max_nodes, form=form)
 
 
 def _temp_state(x, P=None):

@@ -165,7 +165,7 @@ def default_QR():
 
 def sim(filt, waypoints: np.ndarray, landmarks: np.ndarray, seed: int, nlaps: int = 2,
         max_steps: int = 100000, monitor=None, fused: bool = False, prune_after=None, merge_gate=None,
-        submap_steps=None) -> SimLog:
+        submap_steps=None, association: str = "nearest") -> SimLog:
     """The loop of sim/ekfslam-sim.jl:80-141 without sleep/pause.
 
     ``filt`` must already hold the initial state (x = initial pose, P = 0).
@@ -186,7 +186,15 @@ def sim(filt, waypoints: np.ndarray, landmarks: np.ndarray, seed: int, nlaps: in
     joined with ``filt.join(local, merge_gate=merge_gate)``, closed, and a new one starts.  With ``merge_gate`` the join fuses the
     landmarks both maps hold (there is no per-step merge in this mode; ``prune_after`` is refused).  Joins are recorded in
     ``log.joined``; ``log.slam_track`` holds the local pose composed with the frozen global one.
+    ``association``: "nearest" (default) is the reference's nearest neighbour.  "joint" (no counterpart in the reference) takes
+    the decisions from the joint-compatibility search, ``filt.associate_joint`` / ``filt.observe_joint`` with their defaults: no
+    landmark is used twice in one step (at most 64 observations per step; not available with ``submap_steps``).
     """
+    if association not in ("nearest", "joint"):
+        raise ValueError('association must be "nearest" or "joint"')
+    joint = association == "joint"
+    if joint and submap_steps is not None:
+        raise ValueError('association="joint" is not available with submap_steps')
     if submap_steps is not None:
         if prune_after is not None:
             raise ValueError("prune_after counts matches in one map: not available with submap_steps")
@@ -214,11 +222,11 @@ def sim(filt, waypoints: np.ndarray, landmarks: np.ndarray, seed: int, nlaps: in
             dtsum = 0.0
             z, _tags = get_observations(vehicle, landmarks, R, rng)       # :108
             if fused:
-                assoc = np.asarray(filt.observe(z, R, GATE1, GATE2))      # :114-120 in one call
+                assoc = np.asarray(filt.observe_joint(z, R, GATE1, GATE2)[0] if joint else filt.observe(z, R, GATE1, GATE2))   # :114-120 in one call
                 idf = assoc[assoc > 0]
                 zn = np.asarray(z, dtype=float).reshape(2, -1)[:, assoc < 0]
             else:
-                zf, idf, zn = filt.associate(z, R, GATE1, GATE2)          # :114
+                zf, idf, zn = filt.associate_joint(z, R, GATE1, GATE2)[:3] if joint else filt.associate(z, R, GATE1, GATE2)   # :114
                 filt.update(zf, R, idf)                                   # :117
                 filt.add_features(zn, R)                                  # :120
             log.obs_steps.append(nsteps)
