@@ -16,6 +16,7 @@ export SlamState, EKFSlamState, set_state!, predict, update, add_features, assoc
        compute_association, predict_observation, mpi_to_pi,
        ekf_predict!, ekf_update!, augment!, observe!, cov_block, cov_diag, landmark_blocks, gate_mode!, gate_info, state_written!, remove_features!, find_duplicates, merge_landmarks!, transform!, join!, submap, associate_joint, observe_joint!, joint_nis, chi2_table, feature_ellipses, vehicle_ellipse,
        PFSlamState, set_pose!, init_landmarks!, pf_predict!, update_known!, step!, step_async!, step_async_batch!, step_unknown!, LandmarkEvidence, evidence_update!, counters, step_unknown_pruned!, flush!,
+       PathHistory, record!, path_info, path_record, trace, best_path, mean_path, survivors,
        resample!, mean_pose, weights, particles, pf_map, pf_best_particle, peer_blob, attach_peers!, peer_selftest, detach_peers!, comm_info
 
 const libslamhip = get(ENV, "SLAMHIP_LIB", joinpath(@__DIR__, "libslamhip.so"))
@@ -31,6 +32,9 @@ const libslamhip_evidence = get(ENV, "SLAMHIP_EVIDENCE_LIB", joinpath(@__DIR__, 
 # the companion library of include/slamhip_jc.h (joint-compatibility data association for the EKF), same arrangement (opened at the
 # first associate_joint / joint_nis)
 const libslamhip_jc = get(ENV, "SLAMHIP_JC_LIB", joinpath(@__DIR__, "libslamhip_jc.so"))
+# the companion library of include/slamhip_path.h (per-particle trajectory history of the particle filter), same arrangement
+# (opened at the first PathHistory)
+const libslamhip_path = get(ENV, "SLAMHIP_PATH_LIB", joinpath(@__DIR__, "libslamhip_path.so"))
 
 const SLAM_OK = Cint(0)
 const SLAM_PF_HALTED = Cint(1)
@@ -823,6 +827,91 @@ function pf_best_particle(s::PFSlamState)
     check(ccall((:slam_pf_get_particle, libslamhip), Cint, (Ptr{Cvoid}, Int64, Ref{Int64}, Ref{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
                 s.handle, -1, gid, logw, pose, lm))
     gid[], logw[], pose, lm
+end
+
+"""
+    PathHistory(state, cap)
+
+Per-particle trajectory history of a filter (include/slamhip_path.h): a ring of `cap` records on the device, each a snapshot of
+the poses and the ancestors back to the record before.  `record!` makes a record, `resample!(path, gmax, u0)` resamples the
+filter with the history following the particles -- a filter with a path object is resampled through it ONLY --, `trace`,
+`best_path`, `mean_path` and `survivors` follow the CURRENT particles back through the ring (column 1: the oldest held record).
+Only a filter that lives wholly on one rank (`world == 1`).  The object borrows `state` (kept alive through the field).
+"""
+mutable struct PathHistory
+    handle::Ptr{Cvoid}
+    state::PFSlamState
+    cap::Int
+    function PathHistory(s::PFSlamState, cap::Integer)
+        s.world == 1 || error("the path history supports only a filter that lives wholly on one rank")
+        h = Ref{Ptr{Cvoid}}(C_NULL)
+        check(ccall((:slam_pf_path_create, libslamhip_path), Cint, (Ref{Ptr{Cvoid}}, Ptr{Cvoid}, Cint), h, s.handle, cap))
+        p = new(h[], s, cap)
+        finalizer(p) do ph
+            ccall((:slam_pf_path_destroy, libslamhip_path), Cint, (Ptr{Cvoid},), ph.handle)
+        end
+        return p
+    end
+end
+
+"One record: the live poses and the composed ancestors of the resamplings since the last record.  Enqueued."
+function record!(p::PathHistory)
+    check(ccall((:slam_pf_path_record, libslamhip_path), Cint, (Ptr{Cvoid},), p.handle))
+    p
+end
+
+"slam_pf_resample_local with the history following the particles; `gmax`: the largest (normalised) log-weight, `u0` in [0, 1)."
+function resample!(p::PathHistory, gmax::Real, u0::Real)
+    check(ccall((:slam_pf_path_resample, libslamhip_path), Cint, (Ptr{Cvoid}, Cdouble, Cdouble), p.handle, gmax, u0))
+    p
+end
+
+"[records held L, records ever made, cap, resamplings seen]"
+function path_info(p::PathHistory)
+    out = zeros(Int64, 4)
+    check(ccall((:slam_pf_path_info, libslamhip_path), Cint, (Ptr{Cvoid}, Ptr{Int64}), p.handle, out))
+    out
+end
+
+"The record `k` back (0: the newest): (pose n x 3, ancestors n -- 0-based, the identity where none were stored --, stored?)."
+function path_record(p::PathHistory, k::Integer = 0)
+    pose = zeros(Float64, p.state.n, 3)                # the library's [3][n], particle index fastest
+    anc = zeros(Int32, p.state.n)
+    has = Ref{Cint}(0)
+    check(ccall((:slam_pf_path_get, libslamhip_path), Cint, (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Int32}, Ref{Cint}),
+                p.handle, k, pose, anc, has))
+    pose, anc, has[] != 0
+end
+
+"The paths of the current particles `ids` (0-based, at most 4096): 3 x L x length(ids), (x, y, phi), oldest held record first."
+function trace(p::PathHistory, ids::AbstractVector)
+    idv = Vector{Int64}(ids)
+    out = zeros(Float64, 3, max(1, path_info(p)[1]), max(1, length(idv)))
+    check(ccall((:slam_pf_path_trace, libslamhip_path), Cint, (Ptr{Cvoid}, Ptr{Int64}, Cint, Ptr{Cdouble}),
+                p.handle, idv, length(idv), out))
+    out
+end
+
+"(index, 3 x L path) of the particle with the largest log-weight (0-based index, the lowest on a tie)."
+function best_path(p::PathHistory)
+    idx = Ref{Int64}(0)
+    out = zeros(Float64, 3, max(1, path_info(p)[1]))
+    check(ccall((:slam_pf_path_best, libslamhip_path), Cint, (Ptr{Cvoid}, Ref{Int64}, Ptr{Cdouble}), p.handle, idx, out))
+    idx[], out
+end
+
+"The mean path under the current weights: 4 x L, (x, y, phi, mean resultant length of the headings) per record."
+function mean_path(p::PathHistory)
+    out = zeros(Float64, 4, max(1, path_info(p)[1]))
+    check(ccall((:slam_pf_path_mean, libslamhip_path), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), p.handle, out))
+    out
+end
+
+"Distinct particles at each held record that have a descendant among the current particles (the depletion diagnostic)."
+function survivors(p::PathHistory)
+    out = zeros(Int64, max(1, path_info(p)[1]))
+    check(ccall((:slam_pf_path_survivors, libslamhip_path), Cint, (Ptr{Cvoid}, Ptr{Int64}), p.handle, out))
+    out
 end
 
 "Download: (pose 3 x n ... as n x 3, logw n, lm n x 5 x max_landmarks): the device's SoA arrays, particle index fastest."

@@ -15,7 +15,7 @@ from .ekf import (DeviceRef, EKFSlamState, SlamState, add_features, associate, a
                   observe, remove_features, remove_features_, removal_maps, update,
                   find_duplicates, merge_features, merge_features_, merge_in_batches,
                   rigid_fit, transform_features, transform_features_)
-from .pf import (FastSLAM, LandmarkEvidence, PFShard, PFSlamState, TorchComm, attach_local_peers, philox_uniform, shared_page,  # noqa: F401
+from .pf import (FastSLAM, LandmarkEvidence, PathHistory, PFShard, PFSlamState, TorchComm, attach_local_peers, philox_uniform, shared_page,  # noqa: F401
                  small)
 from . import sim  # noqa: F401
 from . import telemetry  # noqa: F401

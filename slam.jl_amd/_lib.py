@@ -331,6 +331,52 @@ def jc_lib():
     return cl
 
 
+# ---- the fifth companion library: per-particle trajectory history for FastSLAM (include/slamhip_path.h) ----------------------
+# Same arrangement again: libslamhip_path.so links against libslamhip.so (run path $ORIGIN), works on its particle-filter
+# handles and is opened when the first path object is made, not at import.
+PATH_LIB_PATH = os.path.join(_HERE, "libslamhip_path.so")
+SLAM_PF_PATH_MAXTRACE = 4096
+
+#: every symbol include/slamhip_path.h declares
+PATH_SIGNATURES = {
+    "slam_pf_path_create": (C.c_int, [C.POINTER(_h), _h, C.c_int]),
+    "slam_pf_path_destroy": (C.c_int, [_h]),
+    "slam_pf_path_record": (C.c_int, [_h]),
+    "slam_pf_path_resample": (C.c_int, [_h, C.c_double, C.c_double]),
+    "slam_pf_path_info": (C.c_int, [_h, _i64p]),
+    "slam_pf_path_get": (C.c_int, [_h, C.c_int, _dp, _ip, C.POINTER(C.c_int)]),
+    "slam_pf_path_trace": (C.c_int, [_h, _i64p, C.c_int, _dp]),
+    "slam_pf_path_best": (C.c_int, [_h, _i64p, _dp]),
+    "slam_pf_path_mean": (C.c_int, [_h, _dp]),
+    "slam_pf_path_survivors": (C.c_int, [_h, _i64p]),
+}
+
+_path = None
+
+
+def path_lib():
+    """libslamhip_path.so, opened on first use.  No fallback: missing or unloadable is an ImportError.  Refuses SLAMHIP_LIBRARY
+    for the reason frame_lib() gives: the handles would belong to another library than the one the companion is linked against."""
+    global _path
+    if _path is not None:
+        return _path
+    if os.path.abspath(LIB_PATH) != os.path.join(_HERE, "libslamhip.so"):
+        raise ImportError(f"libslamhip_path.so is linked against {os.path.join(_HERE, 'libslamhip.so')}; the handles of "
+                          f"{LIB_PATH} (SLAMHIP_LIBRARY) cannot be passed to it")
+    if not os.path.exists(PATH_LIB_PATH):
+        raise ImportError(f"{PATH_LIB_PATH} is missing: build it with `make -C slam.jl_amd/csrc`.  slam.jl_amd has no CPU fallback.")
+    try:
+        pl = C.CDLL(PATH_LIB_PATH)
+    except OSError as e:  # pragma: no cover - depends on the machine
+        raise ImportError(f"cannot load {PATH_LIB_PATH}: {e}.  slam.jl_amd has no CPU fallback.") from e
+    for name, (res, args) in PATH_SIGNATURES.items():
+        fn = getattr(pl, name)
+        fn.restype = res
+        fn.argtypes = args
+    _path = pl
+    return pl
+
+
 def last_error() -> str:
     msg = lib.slam_last_error()
     return msg.decode("utf-8", "replace") if msg else ""

@@ -28,10 +28,10 @@ import sys
 
 import numpy as np
 
-from ._lib import SLAM_F32, SLAM_F64, SLAM_PF_HALTED, SLAM_PF_PEER_BLOB_BYTES, check, evidence_lib, frame_lib, lib
+from ._lib import SLAM_F32, SLAM_F64, SLAM_PF_HALTED, SLAM_PF_PEER_BLOB_BYTES, check, evidence_lib, frame_lib, lib, path_lib
 from .ekf import _obs, _small, _ptr, rigid_fit
 
-__all__ = ["PFShard", "PFSlamState", "FastSLAM", "LandmarkEvidence", "philox_uniform", "small", "shared_page", "attach_local_peers",
+__all__ = ["PFShard", "PFSlamState", "FastSLAM", "LandmarkEvidence", "PathHistory", "philox_uniform", "small", "shared_page", "attach_local_peers",
            "finalise_map", "ellipse_axes", "MapSnapshot"]
 
 _M0, _M1, _W0, _W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
@@ -611,6 +611,91 @@ class LandmarkEvidence:
         return out
 
 
+class PathHistory:
+    """Per-particle trajectory history of a filter (include/slamhip_path.h): a ring of ``cap`` records on the device, each a
+    snapshot of the poses and the ancestors back to the record before, and the read-outs that follow the CURRENT particles
+    back through it -- ``trace`` (the paths of named particles), ``best`` (of the particle with the largest log-weight),
+    ``mean`` (the weighted mean path) and ``survivors`` (distinct ancestors still alive at each record, the depletion
+    diagnostic).  Device memory: cap * (3 * itemsize + 4) * n + 8 n bytes.
+
+    ``shard`` is a :class:`PFShard` that holds the WHOLE filter (no peers; sharded filters are not supported).  The object
+    borrows the shard: close it before the shard.  A filter with a path object is resampled through :meth:`resample`
+    (``FastSLAM.resample`` does once ``FastSLAM.track_path`` has been called) and through nothing else -- otherwise the history
+    no longer belongs to the particles.  Records are held oldest first: index 0 of every read-out is the oldest held record."""
+
+    def __init__(self, shard, cap):
+        self.shard = shard
+        self.cap = int(cap)
+        self._p = C.c_void_p()
+        self._lib = path_lib()
+        check(self._lib.slam_pf_path_create(C.byref(self._p), shard._h, self.cap))
+
+    def close(self):
+        if getattr(self, "_p", None) is not None and self._p:
+            if self.shard._h:                       # (a shard closed first took the stream along: nothing left to free on)
+                self._lib.slam_pf_path_destroy(self._p)
+            self._p = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def record(self):
+        """The live poses into the next slot, with the composed ancestors of the resamplings since the last record
+        (slam_pf_path_record).  Enqueued."""
+        check(self._lib.slam_pf_path_record(self._p))
+
+    def resample(self, gmax, u0):
+        """``PFShard.resample_local`` with the history following the particles (slam_pf_path_resample)."""
+        check(self._lib.slam_pf_path_resample(self._p, float(gmax), float(u0)))
+
+    def info(self):
+        """{L: records held, records: records ever made, cap, resamples: resamplings seen}."""
+        out = np.zeros(4, dtype=np.int64)
+        check(self._lib.slam_pf_path_info(self._p, _ptr(out, C.c_int64)))
+        return dict(L=int(out[0]), records=int(out[1]), cap=int(out[2]), resamples=int(out[3]))
+
+    def _rows(self):
+        return max(1, self.info()["L"])              # (L == 0: the library refuses the read-out; the buffer is never written)
+
+    def get(self, k=0):
+        """The record ``k`` back (0: the newest): (pose [3, n] float64, ancestors [n] int32 -- the identity where none were
+        stored --, ancestors stored?)."""
+        pose = np.empty((3, self.shard.n))
+        anc = np.empty(self.shard.n, dtype=np.int32)
+        has = C.c_int()
+        check(self._lib.slam_pf_path_get(self._p, int(k), _ptr(pose), _ptr(anc, C.c_int32), C.byref(has)))
+        return pose, anc, bool(has.value)
+
+    def trace(self, ids):
+        """The paths of the current particles ``ids`` (at most 4096): [len(ids), L, 3] float64 = (x, y, phi), oldest first."""
+        idv = np.ascontiguousarray(np.asarray(ids, dtype=np.int64).reshape(-1))
+        out = np.empty((max(1, idv.shape[0]), self._rows(), 3))
+        check(self._lib.slam_pf_path_trace(self._p, _ptr(idv, C.c_int64), idv.shape[0], _ptr(out)))
+        return out
+
+    def best(self):
+        """(index, path [L, 3]) of the particle with the largest log-weight (lowest index on a tie)."""
+        idx = C.c_int64()
+        out = np.empty((self._rows(), 3))
+        check(self._lib.slam_pf_path_best(self._p, C.byref(idx), _ptr(out)))
+        return int(idx.value), out
+
+    def mean(self):
+        """The mean path under the current weights: [L, 4] = (x, y, phi, R), R the mean resultant length of the headings."""
+        out = np.empty((self._rows(), 4))
+        check(self._lib.slam_pf_path_mean(self._p, _ptr(out)))
+        return out
+
+    def survivors(self):
+        """int64 [L]: distinct particles at each record that have a descendant among the current particles."""
+        out = np.empty(self._rows(), dtype=np.int64)
+        check(self._lib.slam_pf_path_survivors(self._p, _ptr(out, C.c_int64)))
+        return out
+
+
 class _SingleProcess:
     """The world of one rank."""
     rank, world = 0, 1
@@ -756,9 +841,32 @@ class FastSLAM:
         self.force_exchange = False                 # measurement only: take the multi-rank resampling flow on one rank
         self._gmax_norm = None                      # max log-weight after the last normalize() (None: unknown)
         self.resamples = 0
+        self.path_history = None                    # a PathHistory once track_path() has been called
         self.last_neff = float(shard.n_global)
         assert shard.n * self.comm.world == shard.n_global and shard.first == self.comm.rank * shard.n, (
             "ranks must own equal, contiguous slices in rank order")
+
+    def track_path(self, cap):
+        """Keep the particles' trajectories from here on: a :class:`PathHistory` of ``cap`` records (returned, and kept as
+        ``self.path_history``).  From then on ``resample()`` goes through it, the synchronous ``step`` / ``step_unknown`` /
+        ``step_unknown_fused`` make one record at their end, and the enqueued steps (``step_async*``: their resampling stays on
+        the device) and ``step_unknown_pruned`` (its resampling goes through the evidence object) raise.  Whole filter on one
+        rank only."""
+        if self.comm.world != 1 or self.shard.n != self.shard.n_global:
+            raise ValueError("the path history supports only a filter that lives wholly on one rank")
+        if self.path_history is not None:
+            self.path_history.close()
+        self.path_history = PathHistory(self.shard, cap)
+        return self.path_history
+
+    def _record_path(self):
+        if self.path_history is not None:
+            self.path_history.record()
+
+    def _no_path(self, what):
+        if self.path_history is not None:
+            raise RuntimeError(f"{what} cannot be used while the filter tracks its path (FastSLAM.track_path): its resampling "
+                               "does not go through the path history")
 
     def predict(self, V, G, wheelbase, Q, dt):
         self.shard.predict(V, G, wheelbase, Q, dt)
@@ -799,6 +907,10 @@ class FastSLAM:
         sh, comm = self.shard, self.comm
         u0 = philox_uniform(self.resamples, STREAM_RESAMPLE, sh.seed)
         local = getattr(sh, "resample_local", None)
+        if self.path_history is not None:
+            if self.force_exchange or self._gmax_norm is None:
+                raise RuntimeError("a filter that tracks its path resamples after normalize(), through the path history only")
+            local = self.path_history.resample                          # the same call, the history follows the particles
         if comm.world == 1 and not self.force_exchange and local is not None and self._gmax_norm is not None:
             local(self._gmax_norm, u0)                                  # the whole filter on one GPU: one library call
             self._gmax_norm = None
@@ -863,6 +975,7 @@ class FastSLAM:
         do = force_resample if force_resample is not None else (neff < self.neff_frac * self.shard.n_global)
         if do:
             self.resample()
+        self._record_path()
         return neff, bool(do)
 
     # -- the same step without the host in the loop --------------------------------------------------------------------
@@ -872,6 +985,7 @@ class FastSLAM:
         device too.  A sharded filter resamples through the host (all-gather of the log-weights + record exchange): the
         library halts at such a step, skips what was queued behind it, and this method resolves the halt the moment
         the library reports it -- resample(), resume (the skipped steps are enqueued again), carry on."""
+        self._no_path("step_async")
         self._gmax_norm = None
         sh = self.shard
         while sh.step_auto(V, G, wheelbase, Q, dt, z, ids, R, neff_frac=self.neff_frac, force=force_resample,
@@ -881,6 +995,7 @@ class FastSLAM:
     def step_async_batch(self, batch, wheelbase, Q, dt, R, proposal=False, persistent=False):
         """K ``step_async`` calls as one (shard.step_auto_batch, ``batch`` from PFShard.prepare_batch); ``persistent=True`` allows
         persistent launches of up to 16 steps (see there).  Halts of the sharded halting flow are resolved on the way."""
+        self._no_path("step_async_batch")
         self._gmax_norm = None
         sh = self.shard
         k, K = 0, batch[0]
@@ -918,6 +1033,7 @@ class FastSLAM:
         do = force_resample if force_resample is not None else (neff < self.neff_frac * self.shard.n_global)
         if do:
             self.resample()
+        self._record_path()
         return neff, bool(do)
 
     def step_unknown_fused(self, V, G, wheelbase, Q, dt, z, R, gate1, gate2, force_resample=None):
@@ -928,6 +1044,7 @@ class FastSLAM:
         do = force_resample if force_resample is not None else (neff < self.neff_frac * self.shard.n_global)
         if do:
             self.resample()
+        self._record_path()
         return neff, bool(do)
 
     def step_unknown_pruned(self, V, G, wheelbase, Q, dt, z, R, gate1, gate2, evidence, force_resample=None):
@@ -937,6 +1054,7 @@ class FastSLAM:
         touches no weight.  Whole filter on one rank only.  Returns (Neff, resampled?, counts) with counts = [records in
         use, created, decremented, pruned] of this step."""
         assert self.comm.world == 1, "landmark evidence supports only a filter that lives wholly on one rank"
+        self._no_path("step_unknown_pruned")
         self._gmax_norm = None
         stats, counts = evidence.step(V, G, wheelbase, Q, dt, z, R, gate1, gate2)
         neff = self.normalize(stats)
@@ -1124,9 +1242,25 @@ class PFSlamState(FastSLAM):
         """[cx, cy, vehicle_phi, rx, ry, phi] of the particles' pose cloud."""
         return MapSnapshot(self.map_sums([])).vehicle_ellipse()
 
+    def path(self):
+        """The path of the particle with the largest log-weight, [L, 3] = (x, y, phi), oldest held record first
+        (``track_path`` first; PathHistory.best)."""
+        if self.path_history is None:
+            raise RuntimeError("the filter does not track its path: call track_path(cap) first")
+        return self.path_history.best()[1]
+
+    def mean_path(self):
+        """The mean path under the current weights, [L, 4] = (x, y, phi, R) (``track_path`` first; PathHistory.mean)."""
+        if self.path_history is None:
+            raise RuntimeError("the filter does not track its path: call track_path(cap) first")
+        return self.path_history.mean()
+
     def close(self):
         """Collective for a sharded filter with peers: remote records are brought home, the peers are detached, then a
         barrier -- nobody frees buffers a peer may still read."""
+        if getattr(self, "path_history", None) is not None:
+            self.path_history.close()
+            self.path_history = None
         if getattr(self, "peers", False):
             import torch.distributed as dist
             trace = os.environ.get("SLAMHIP_TRACE_CLOSE") == "1"

@@ -143,6 +143,7 @@ class SimLog:
     joined: list = field(default_factory=list)          # (observation step, first_new, landmarks joined, landmarks after) per join (sim(submap_steps=k))
     true_track: list = field(default_factory=list)
     slam_track: list = field(default_factory=list)
+    best_path: object = None                            # [L, 3]: the best particle's path at the end of the run (a PFSlamState after track_path)
 
 
 #: constants of sim/ekfslam-sim.jl:62-76,114
@@ -261,6 +262,8 @@ def sim(filt, waypoints: np.ndarray, landmarks: np.ndarray, seed: int, nlaps: in
         log.slam_track.append(np.array(filt.pose()))
         if monitor is not None:
             monitor(vehicle, filt, nsteps)
+    if getattr(filt, "path_history", None) is not None:                   # a PFSlamState that tracks its path (FastSLAM.track_path)
+        log.best_path = np.array(filt.path())
     return log
 
 
