@@ -14,7 +14,7 @@ module SLAMHip
 
 export SlamState, EKFSlamState, set_state!, predict, update, add_features, associate,
        compute_association, predict_observation, mpi_to_pi,
-       ekf_predict!, ekf_update!, augment!, observe!, cov_block, cov_diag, landmark_blocks, gate_mode!, gate_info, state_written!, remove_features!, find_duplicates, merge_landmarks!, transform!, join!, submap, associate_joint, observe_joint!, joint_nis, chi2_table, feature_ellipses, vehicle_ellipse,
+       ekf_predict!, ekf_update!, augment!, observe!, cov_block, cov_diag, landmark_blocks, gate_mode!, gate_info, state_written!, remove_features!, find_duplicates, merge_landmarks!, transform!, join!, submap, select, reserve!, capacity, associate_joint, observe_joint!, joint_nis, chi2_table, feature_ellipses, vehicle_ellipse,
        PFSlamState, set_pose!, init_landmarks!, pf_predict!, update_known!, step!, step_async!, step_async_batch!, step_unknown!, LandmarkEvidence, evidence_update!, counters, step_unknown_pruned!, flush!,
        PathHistory, record!, path_info, path_record, trace, best_path, mean_path, survivors,
        resample!, mean_pose, weights, particles, pf_map, pf_best_particle, peer_blob, attach_peers!, peer_selftest, detach_peers!, comm_info
@@ -35,9 +35,13 @@ const libslamhip_jc = get(ENV, "SLAMHIP_JC_LIB", joinpath(@__DIR__, "libslamhip_
 # the companion library of include/slamhip_path.h (per-particle trajectory history of the particle filter), same arrangement
 # (opened at the first PathHistory)
 const libslamhip_path = get(ENV, "SLAMHIP_PATH_LIB", joinpath(@__DIR__, "libslamhip_path.so"))
+# the companion library of include/slamhip_copy.h (an EKF state copied, grown or extracted between two handles), same arrangement
+# (opened at the first copy / select / reserve! / capacity)
+const libslamhip_copy = get(ENV, "SLAMHIP_COPY_LIB", joinpath(@__DIR__, "libslamhip_copy.so"))
 
 const SLAM_OK = Cint(0)
 const SLAM_PF_HALTED = Cint(1)
+const SLAM_E_CAPACITY = Cint(-2)
 const SLAM_E_NOTPD = Cint(-3)
 const SLAM_F32 = Cint(0)
 const SLAM_F64 = Cint(1)
@@ -55,23 +59,27 @@ end
 abstract type SlamState end                       # src/common.jl:22
 
 """
-    EKFSlamState(x, cov; max_landmarks, device=0)
+    EKFSlamState(x, cov; max_landmarks, device=0, grow=false)
 
 Device-resident counterpart of `EKFSlamState{T}` (src/common.jl:25-28).  `T` is
 `Float32` or `Float64`.  `state.x` / `state.cov` download on access; assigning them
 uploads.  Capacity is fixed at construction (the reference re-allocates `P` per
-new feature, src/ekf.jl:108-109).
+new feature, src/ekf.jl:108-109) unless `grow = true`: then `augment!`, `observe!`,
+`observe_joint!` and `join!` answer a full map by `reserve!(state, max(2 capacity, needed))`
+and finish the step in the larger handle.
 """
 mutable struct EKFSlamState{T<:Union{Float32,Float64}} <: SlamState
     handle::Ptr{Cvoid}
     device::Int                                   # the device the handle lives on (submap creates its local map there)
     jc::Ptr{Cvoid}                                # the joint-compatibility search workspace (slam_ekf_jc_create), C_NULL until first used
+    grow::Bool                                    # a full map moves into a larger handle (reserve!) instead of failing
+    gate::Cint                                    # the gate mode set through gate_mode! (-1: never set), applied again by reserve!
     function EKFSlamState{T}(x::AbstractVector, cov::AbstractMatrix;
-                             max_landmarks::Integer = max(64, length(x) - 3), device::Integer = 0) where {T}
+                             max_landmarks::Integer = max(64, length(x) - 3), device::Integer = 0, grow::Bool = false) where {T}
         h = Ref{Ptr{Cvoid}}(C_NULL)
         check(ccall((:slam_ekf_create, libslamhip), Cint, (Ref{Ptr{Cvoid}}, Cint, Cint, Cint),
                     h, T === Float32 ? SLAM_F32 : SLAM_F64, max_landmarks, device))
-        s = new{T}(h[], Int(device), C_NULL)
+        s = new{T}(h[], Int(device), C_NULL, grow, Cint(-1))
         finalizer(s) do st
             getfield(st, :jc) == C_NULL || ccall((:slam_ekf_jc_destroy, libslamhip_jc), Cint, (Ptr{Cvoid},), getfield(st, :jc))   # it borrows the handle: first
             ccall((:slam_ekf_destroy, libslamhip), Cint, (Ptr{Cvoid},), getfield(st, :handle))
@@ -161,12 +169,18 @@ function ekf_update!(s::EKFSlamState, z::AbstractMatrix, R::AbstractMatrix, idf;
     s
 end
 
-"add_features (src/ekf.jl:84-122) in place on the device."
+"add_features (src/ekf.jl:84-122) in place on the device.  A growing state (`grow = true`) that is full reserves room first."
 function augment!(s::EKFSlamState, z::AbstractMatrix, R::AbstractMatrix)
     nn = size(z, 2)
     nn == 0 && return s
-    check(ccall((:slam_ekf_augment, libslamhip), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Cint, Ptr{Cdouble}),
-                handle(s), pairs64(z), nn, colmajor4(R)))
+    call() = ccall((:slam_ekf_augment, libslamhip), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Cint, Ptr{Cdouble}),
+                   handle(s), pairs64(z), nn, colmajor4(R))
+    rc = call()
+    if rc == SLAM_E_CAPACITY && getfield(s, :grow)          # decided before anything was enqueued: grow, then again
+        grow_for!(s, nlandmarks(s) + nn)
+        rc = call()
+    end
+    check(rc)
     s
 end
 
@@ -182,9 +196,15 @@ function observe!(s::EKFSlamState, z::AbstractMatrix, R::AbstractMatrix, gate1::
     nz = size(z, 2)
     assoc = zeros(Int32, nz)
     nz == 0 && return assoc
-    check(ccall((:slam_ekf_observe, libslamhip), Cint,
-                (Ptr{Cvoid}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cdouble, Cdouble, Cint, Ptr{Int32}),
-                handle(s), pairs64(z), nz, colmajor4(R), gate1, gate2, form == :joseph ? 1 : 0, assoc))
+    rc = ccall((:slam_ekf_observe, libslamhip), Cint,
+               (Ptr{Cvoid}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cdouble, Cdouble, Cint, Ptr{Int32}),
+               handle(s), pairs64(z), nz, colmajor4(R), gate1, gate2, form == :joseph ? 1 : 0, assoc)
+    if rc == SLAM_E_CAPACITY && getfield(s, :grow)
+        # the association vector is complete and the update has been applied; only the new features are missing
+        augment!(s, pairs64(z)[:, assoc .< 0], R)
+        return assoc
+    end
+    check(rc)
     assoc
 end
 
@@ -222,6 +242,7 @@ reach (O(candidates)), `:auto` (default) takes the grid from 16384 landmarks on.
 function gate_mode!(s::EKFSlamState, mode::Symbol)
     m = mode === :auto ? 0 : mode === :sweep ? 1 : mode === :grid ? 2 : throw(ArgumentError("gate mode must be :auto, :sweep or :grid"))
     check(ccall((:slam_ekf_set_gate_mode, libslamhip), Cint, (Ptr{Cvoid}, Cint), handle(s), m))
+    setfield!(s, :gate, Cint(m))
     s
 end
 
@@ -323,7 +344,13 @@ and the composed `new_index` (one entry per landmark of the joined map) is retur
 """
 function join!(a::EKFSlamState{T}, b::EKFSlamState{T}; merge_gate = nothing, Rc = nothing) where {T}
     first = Ref{Int32}(0)
-    check(ccall((:slam_ekf_join, libslamhip_join), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ref{Int32}), handle(a), handle(b), first))
+    call() = ccall((:slam_ekf_join, libslamhip_join), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ref{Int32}), handle(a), handle(b), first)
+    rc = call()
+    if rc == SLAM_E_CAPACITY && getfield(a, :grow)          # decided before anything was enqueued: grow, then again
+        grow_for!(a, nlandmarks(a) + nlandmarks(b))
+        rc = call()
+    end
+    check(rc)
     merge_gate === nothing && return Int(first[])
     cur = collect(Int32, 1:nlandmarks(a))
     while true
@@ -341,6 +368,79 @@ function join!(a::EKFSlamState{T}, b::EKFSlamState{T}; merge_gate = nothing, Rc 
     end
     Int(first[]), cur
 end
+
+# ---- a state moved between two handles on the device (include/slamhip_copy.h) ---------------------------------------------------
+"The landmark capacity of the handle (slam_ekf_capacity)."
+function capacity(s::EKFSlamState)
+    out = Ref{Cint}(0)
+    check(ccall((:slam_ekf_capacity, libslamhip_copy), Cint, (Ptr{Cvoid}, Ref{Cint}), handle(s), out))
+    Int(out[])
+end
+
+blank(s::EKFSlamState{T}, max_landmarks::Integer) where {T} =
+    EKFSlamState{T}(zeros(T, 3), zeros(T, 3, 3); max_landmarks = max_landmarks, device = getfield(s, :device), grow = getfield(s, :grow))
+
+"""
+    copy!(dst, src) -> dst
+
+`dst` becomes `src` on the device (slam_ekf_copy): N, x and every entry of cov, bit for bit.  The capacities may differ in either
+direction as long as `src`'s landmarks fit `dst`.  `src` is only read.  Enqueued, does not synchronise.
+"""
+function Base.copy!(dst::EKFSlamState{T}, src::EKFSlamState{T}) where {T}
+    check(ccall((:slam_ekf_copy, libslamhip_copy), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), handle(dst), handle(src)))
+    dst
+end
+
+"    copy(s; max_landmarks = capacity(s)) -> a new state on the same device that holds `s` (`copy!`): a fork to try a hypothesis on."
+Base.copy(s::EKFSlamState; max_landmarks::Integer = capacity(s)) = copy!(blank(s, max_landmarks), s)
+
+"""
+    select(s, ids; max_landmarks = max(64, 2 length(ids))) -> EKFSlamState
+
+The sub-map `ids` (1-based, distinct, any order; none: the vehicle alone) of `s` with its full marginal covariance, in a new state on
+the same device (slam_ekf_select): its landmark k is `s`'s landmark `ids[k]`, x = x[sel], cov = cov[sel, sel], bit for bit.
+"""
+function select(s::EKFSlamState, ids::AbstractVector{<:Integer}; max_landmarks::Integer = max(64, 2 * length(ids)))
+    dst = blank(s, max_landmarks)
+    sel = collect(Int32, ids)
+    check(ccall((:slam_ekf_select, libslamhip_copy), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int32}, Cint),
+                handle(dst), handle(s), sel, length(sel)))
+    dst
+end
+
+"""
+    reserve!(s, max_landmarks) -> s
+
+Make room for `max_landmarks` landmarks (nothing happens if the capacity is already that large): a new handle is created, the state
+is copied into it on the device, it takes the old handle's place inside `s` and the old one is destroyed.  The gate mode set through
+`gate_mode!` is applied again; the joint-association workspace is dropped and made again at the next joint call.  Raw device pointers
+obtained before are dead afterwards.  Old and new matrix exist side by side during the call.
+"""
+function reserve!(s::EKFSlamState{T}, max_landmarks::Integer) where {T}
+    max_landmarks <= capacity(s) && return s
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:slam_ekf_create, libslamhip), Cint, (Ref{Ptr{Cvoid}}, Cint, Cint, Cint),
+                h, T === Float32 ? SLAM_F32 : SLAM_F64, max_landmarks, getfield(s, :device)))
+    rc = ccall((:slam_ekf_copy, libslamhip_copy), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), h[], handle(s))
+    if rc == SLAM_OK && getfield(s, :gate) >= 0
+        rc = ccall((:slam_ekf_set_gate_mode, libslamhip), Cint, (Ptr{Cvoid}, Cint), h[], getfield(s, :gate))
+    end
+    if rc != SLAM_OK
+        ccall((:slam_ekf_destroy, libslamhip), Cint, (Ptr{Cvoid},), h[])
+        check(rc)
+    end
+    if getfield(s, :jc) != C_NULL                            # it borrows the old handle
+        ccall((:slam_ekf_jc_destroy, libslamhip_jc), Cint, (Ptr{Cvoid},), getfield(s, :jc))
+        setfield!(s, :jc, C_NULL)
+    end
+    old = handle(s)
+    setfield!(s, :handle, h[])
+    ccall((:slam_ekf_destroy, libslamhip), Cint, (Ptr{Cvoid},), old)      # (waits for the copy's last read of it)
+    s
+end
+
+"The growth rule of a growing state: twice the capacity, or what is needed if that is more."
+grow_for!(s::EKFSlamState, needed::Integer) = reserve!(s, max(2 * capacity(s), needed))
 
 "feature_ellipses(x, cov) of the browser monitor (sim/browser/wsserver.jl:72-85): 5 x N [cx; cy; rx; ry; phi], on the device."
 function feature_ellipses(s::EKFSlamState)

@@ -14,7 +14,8 @@ from .ekf import (DeviceRef, EKFSlamState, SlamState, add_features, associate, a
                   compute_association, ekf_predict_, ekf_update_, mpi_to_pi, predict, predict_observation,
                   observe, remove_features, remove_features_, removal_maps, update,
                   find_duplicates, merge_features, merge_features_, merge_in_batches,
-                  rigid_fit, transform_features, transform_features_)
+                  rigid_fit, transform_features, transform_features_,
+                  copy_state, select_features, select_map, grown_capacity)
 from .pf import (FastSLAM, LandmarkEvidence, PathHistory, PFShard, PFSlamState, TorchComm, attach_local_peers, philox_uniform, shared_page,  # noqa: F401
                  small)
 from . import sim  # noqa: F401

@@ -377,6 +377,44 @@ def path_lib():
     return pl
 
 
+# ---- the sixth companion library: an EKF state copied, grown or extracted between two handles (include/slamhip_copy.h) --------
+# Same arrangement again: libslamhip_copy.so links against libslamhip.so (run path $ORIGIN), works on its EKF handles and is
+# opened at the first copy, not at import.
+COPY_LIB_PATH = os.path.join(_HERE, "libslamhip_copy.so")
+
+#: every symbol include/slamhip_copy.h declares
+COPY_SIGNATURES = {
+    "slam_ekf_capacity": (C.c_int, [_h, C.POINTER(C.c_int)]),
+    "slam_ekf_copy": (C.c_int, [_h, _h]),
+    "slam_ekf_select": (C.c_int, [_h, _h, _ip, C.c_int]),
+}
+
+_copy = None
+
+
+def copy_lib():
+    """libslamhip_copy.so, opened on first use.  No fallback: missing or unloadable is an ImportError.  Refuses SLAMHIP_LIBRARY
+    for the reason frame_lib() gives: the handles would belong to another library than the one the companion is linked against."""
+    global _copy
+    if _copy is not None:
+        return _copy
+    if os.path.abspath(LIB_PATH) != os.path.join(_HERE, "libslamhip.so"):
+        raise ImportError(f"libslamhip_copy.so is linked against {os.path.join(_HERE, 'libslamhip.so')}; the handles of "
+                          f"{LIB_PATH} (SLAMHIP_LIBRARY) cannot be passed to it")
+    if not os.path.exists(COPY_LIB_PATH):
+        raise ImportError(f"{COPY_LIB_PATH} is missing: build it with `make -C slam.jl_amd/csrc`.  slam.jl_amd has no CPU fallback.")
+    try:
+        yl = C.CDLL(COPY_LIB_PATH)
+    except OSError as e:  # pragma: no cover - depends on the machine
+        raise ImportError(f"cannot load {COPY_LIB_PATH}: {e}.  slam.jl_amd has no CPU fallback.") from e
+    for name, (res, args) in COPY_SIGNATURES.items():
+        fn = getattr(yl, name)
+        fn.restype = res
+        fn.argtypes = args
+    _copy = yl
+    return yl
+
+
 def last_error() -> str:
     msg = lib.slam_last_error()
     return msg.decode("utf-8", "replace") if msg else ""

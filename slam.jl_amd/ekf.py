@@ -36,6 +36,7 @@ __all__ = [
     "remove_features", "remove_features_", "removal_maps",
     "find_duplicates", "merge_features", "merge_features_", "merge_in_batches",
     "chi2_table", "associate_joint", "observe_joint",
+    "copy_state", "select_features", "select_map", "grown_capacity",
 ]
 
 _DTYPES = {"f32": (SLAM_F32, np.float32), "f64": (SLAM_F64, np.float64),
@@ -92,6 +93,29 @@ def removal_maps(N, ids):
     new_index = np.zeros(N, dtype=np.int32)
     new_index[left] = np.arange(1, left.size + 1, dtype=np.int32)
     return keep, new_index
+
+
+def select_map(N, ids):
+    """The index map of a selection, as slam_ekf_select forms it on the device (restated here for callers that carry their own
+    per-landmark tables, and for the CPU tests): ``s`` (int32, 3 + 2 len(ids) 0-based state indices of the source, the vehicle
+    first, then the two rows of landmark ids[k] for every k in the order given) -- x[s], P[s][:, s] is the selected state.
+    ``ids``: 1-based, distinct, any order; ValueError for an id outside 1..N or a repeated one (the library: SLAM_E_BADARG)."""
+    ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+    if ids.size and (ids.min() < 1 or ids.max() > N):
+        raise ValueError("landmark id out of range")
+    if np.unique(ids).size != ids.size:
+        raise ValueError("duplicate landmark id")
+    f = 3 + 2 * (ids - 1)
+    return np.concatenate([np.arange(3), np.stack([f, f + 1], axis=1).reshape(-1)]).astype(np.int32)
+
+
+def grown_capacity(capacity, needed):
+    """The capacity a growing state (``grow=True``) reserves when ``needed`` landmarks do not fit ``capacity``: twice the
+    capacity, or what is needed if that is more -- the amortised doubling of the reference's re-allocation."""
+    capacity, needed = int(capacity), int(needed)
+    if capacity < 0 or needed < 0:
+        raise ValueError("capacity and needed must not be negative")
+    return max(2 * capacity, needed)
 
 
 def merge_in_batches(N, pairs, merge_call, batch_max=_lib.SLAM_MERGE_MAX):
@@ -249,10 +273,15 @@ class EKFSlamState(SlamState):
 
     ``max_landmarks`` fixes the capacity (the reference grows P by reallocating,
     src/ekf.jl:108-109); ``dtype`` is "f32" or "f64" (reference: Float64).
+    With ``grow=True`` the capacity follows the map instead: where add_features, observe, observe_joint or join would stop with
+    SLAM_E_CAPACITY the state moves into a larger handle on the device (:meth:`reserve`) and the step is finished there.
     """
 
-    def __init__(self, x, cov, dtype="f64", max_landmarks=None, device=0):
+    def __init__(self, x, cov, dtype="f64", max_landmarks=None, device=0, grow=False):
         code, npdt = _DTYPES[dtype]
+        self.grow = bool(grow)
+        self._gate_mode = None                   # what the caller set through this object: re-applied by reserve()
+        self._async = None
         x = np.asarray(x)
         n = int(x.shape[0])
         if n < 3 or (n - 3) % 2:
@@ -299,6 +328,90 @@ class EKFSlamState(SlamState):
     @property
     def n(self):
         return 3 + 2 * self.N
+
+    @property
+    def capacity(self):
+        """The landmark capacity of the handle (slam_ekf_capacity)."""
+        out = C.c_int()
+        check(_lib.copy_lib().slam_ekf_capacity(self._h, C.byref(out)))
+        return out.value
+
+    # -- a state moved between two handles on the device (include/slamhip_copy.h) --------------
+    def copy_from(self, other):
+        """This state becomes ``other``'s (slam_ekf_copy): N, x and every entry of cov, bit for bit, on the device.  The
+        capacities may differ in either direction as long as other.N fits this one.  ``other`` is only read and may be updated
+        or closed right away; gate mode, async flag and timing of this object stay its own.  Enqueued, does not synchronise."""
+        if not isinstance(other, EKFSlamState):
+            raise TypeError("copy_from needs another EKFSlamState")
+        check(_lib.copy_lib().slam_ekf_copy(self._h, other._h))
+
+    def select_from(self, other, ids):
+        """This state becomes the marginal of ``other`` over the vehicle and the landmarks ``ids`` (1-based, distinct, any order;
+        none: the vehicle alone), on the device (slam_ekf_select): landmark k here is ``other``'s landmark ids[k - 1], x = x[s],
+        cov = cov[s][:, s] with s = select_map(other.N, ids), bit for bit."""
+        if not isinstance(other, EKFSlamState):
+            raise TypeError("select_from needs another EKFSlamState")
+        ids = np.ascontiguousarray(np.asarray(ids, dtype=np.int32).reshape(-1))
+        check(_lib.copy_lib().slam_ekf_select(self._h, other._h, _ptr(ids, C.c_int32) if ids.size else None, int(ids.size)))
+
+    def _blank(self, max_landmarks):
+        return EKFSlamState(np.zeros(3), np.zeros((3, 3)), dtype=self.np_dtype, max_landmarks=int(max_landmarks),
+                            device=self.device, grow=self.grow)
+
+    def copy(self, max_landmarks=None):
+        """A new state on the same device that holds this one (copy_from), with this one's capacity or ``max_landmarks``: a fork
+        to try a hypothesis on."""
+        new = self._blank(self.capacity if max_landmarks is None else max_landmarks)
+        try:
+            new.copy_from(self)
+        except Exception:
+            new.close()
+            raise
+        return new
+
+    def select(self, ids, max_landmarks=None):
+        """A new state on the same device that holds the sub-map ``ids`` of this one with its full marginal covariance
+        (select_from); ``max_landmarks`` as in the constructor (default max(64, 2 len(ids)))."""
+        cnt = int(np.asarray(ids).size)
+        new = self._blank(max(64, 2 * cnt) if max_landmarks is None else max_landmarks)
+        try:
+            new.select_from(self, ids)
+        except Exception:
+            new.close()
+            raise
+        return new
+
+    def reserve(self, max_landmarks):
+        """Make room for ``max_landmarks`` landmarks (nothing happens if the capacity is already that large): a new handle of
+        that capacity is created, the state is copied into it on the device (slam_ekf_copy), the new handle takes the old
+        one's place inside this object and the old one is destroyed.  The gate mode and the async flag set through this object
+        are applied to the new handle; kernel timing starts switched off, and the joint-association workspace is dropped and
+        made again at the next joint call.  Raw device pointers (:meth:`device_ptrs`) obtained before are DEAD afterwards;
+        ``DeviceRef``s stay valid because they go through this object.  Old and new matrix exist side by side during the call."""
+        max_landmarks = int(max_landmarks)
+        if max_landmarks <= self.capacity:
+            return
+        code = _DTYPES[self.np_dtype][0]
+        new = C.c_void_p()
+        check(lib.slam_ekf_create(C.byref(new), code, max_landmarks, self.device))
+        try:
+            check(_lib.copy_lib().slam_ekf_copy(new, self._h))
+            if self._gate_mode is not None:
+                check(lib.slam_ekf_set_gate_mode(new, self.GATE_MODES[self._gate_mode]))
+            if self._async is not None:
+                check(lib.slam_ekf_set_async(new, 1 if self._async else 0))
+        except Exception:
+            lib.slam_ekf_destroy(new)
+            raise
+        if getattr(self, "_jc", None):
+            _lib.jc_lib().slam_ekf_jc_destroy(self._jc)               # it borrows the old handle
+            self._jc = None
+        old, self._h = self._h, new
+        self.max_landmarks = max_landmarks
+        lib.slam_ekf_destroy(old)                                     # (waits for the copy's last read of it)
+
+    def _grow_for(self, needed):
+        self.reserve(grown_capacity(self.capacity, needed))
 
     # -- state I/O --------------------------------------------------------------------
     def set_state(self, x, cov):
@@ -352,6 +465,7 @@ class EKFSlamState(SlamState):
         "sweep" = every landmark, "grid" = the uniform grid over the landmark means (O(candidates)), "auto" = the grid
         from 16384 landmarks on.  Decisions are identical in every mode."""
         check(lib.slam_ekf_set_gate_mode(self._h, self.GATE_MODES[mode]))
+        self._gate_mode = mode
 
     def gate_info(self):
         """slam_ekf_gate_info as a dict: which form the last gating used, the grid's size, and what the grid queries have
@@ -466,7 +580,11 @@ class EKFSlamState(SlamState):
         if zp.shape[0] == 0:
             return
         r = _small(R)
-        check(lib.slam_ekf_augment(self._h, _ptr(zp), zp.shape[0], _ptr(r)))
+        rc = lib.slam_ekf_augment(self._h, _ptr(zp), zp.shape[0], _ptr(r))
+        if rc == _lib.SLAM_E_CAPACITY and self.grow:                  # decided before anything was enqueued: grow, then again
+            self._grow_for(self.N + zp.shape[0])
+            rc = lib.slam_ekf_augment(self._h, _ptr(zp), zp.shape[0], _ptr(r))
+        check(rc)
 
     def remove_landmarks(self, ids):
         """Take the landmarks ``ids`` (1-based, as idf; any order) out of the map, in place on the device
@@ -532,7 +650,11 @@ class EKFSlamState(SlamState):
         if not isinstance(other, EKFSlamState):
             raise TypeError("join needs another EKFSlamState")
         first = C.c_int32()
-        check(_lib.join_lib().slam_ekf_join(self._h, other._h, C.byref(first)))
+        rc = _lib.join_lib().slam_ekf_join(self._h, other._h, C.byref(first))
+        if rc == _lib.SLAM_E_CAPACITY and self.grow:                  # decided before anything was enqueued: grow, then again
+            self._grow_for(self.N + other.N)
+            rc = _lib.join_lib().slam_ekf_join(self._h, other._h, C.byref(first))
+        check(rc)
         if merge_gate is None:
             return first.value
         cur = np.arange(1, self.N + 1, dtype=np.int64)
@@ -577,8 +699,14 @@ class EKFSlamState(SlamState):
         if nz:
             r = _small(R)
             code = SLAM_FORM_JOSEPH if form == "joseph" else SLAM_FORM_CHOLESKY
-            check(lib.slam_ekf_observe(self._h, _ptr(zp), nz, _ptr(r), float(gate1), float(gate2), code,
-                                       _ptr(assoc, C.c_int32)))
+            rc = lib.slam_ekf_observe(self._h, _ptr(zp), nz, _ptr(r), float(gate1), float(gate2), code, _ptr(assoc, C.c_int32))
+            if rc == _lib.SLAM_E_CAPACITY and self.grow:
+                # the association vector is complete and the update has been applied (slam_ekf_observe reports the capacity
+                # behind the update's own status); only the new features are missing: grow, then append them
+                new = np.ascontiguousarray(zp[assoc < 0])
+                self._grow_for(self.N + new.shape[0])
+                rc = lib.slam_ekf_augment(self._h, _ptr(new), new.shape[0], _ptr(r))
+            check(rc)
         return assoc
 
     # -- joint-compatibility data association (include/slamhip_jc.h) ---------------------------
@@ -661,6 +789,7 @@ class EKFSlamState(SlamState):
     # -- stream / timing ----------------------------------------------------------------
     def set_async(self, flag=True):
         check(lib.slam_ekf_set_async(self._h, 1 if flag else 0))
+        self._async = bool(flag)
 
     def sync(self):
         check(lib.slam_ekf_sync(self._h))
@@ -841,6 +970,16 @@ def transform_features_(state, tx, ty, theta):
     st = _state_of(state)
     st.transform(tx, ty, theta)
     return st
+
+
+def copy_state(state: EKFSlamState, max_landmarks=None):
+    """A copy of the state on the device -> a new EKFSlamState (see EKFSlamState.copy)."""
+    return _state_of(state).copy(max_landmarks)
+
+
+def select_features(state: EKFSlamState, ids, max_landmarks=None):
+    """The sub-map ``ids`` with its marginal covariance -> a new EKFSlamState (see EKFSlamState.select)."""
+    return _state_of(state).select(ids, max_landmarks)
 
 
 def find_duplicates(state: EKFSlamState, gate, cap=1024):
