@@ -17,7 +17,7 @@ export SlamState, EKFSlamState, set_state!, predict, update, add_features, assoc
        ekf_predict!, ekf_update!, augment!, observe!, cov_block, cov_diag, landmark_blocks, gate_mode!, gate_info, state_written!, remove_features!, find_duplicates, merge_landmarks!, transform!, join!, submap, select, reserve!, capacity, associate_joint, observe_joint!, joint_nis, chi2_table, feature_ellipses, vehicle_ellipse,
        PFSlamState, set_pose!, init_landmarks!, pf_predict!, update_known!, step!, step_async!, step_async_batch!, step_unknown!, LandmarkEvidence, evidence_update!, counters, step_unknown_pruned!, flush!,
        PathHistory, record!, path_info, path_record, trace, best_path, mean_path, survivors,
-       resample!, mean_pose, weights, particles, pf_map, pf_best_particle, peer_blob, attach_peers!, peer_selftest, detach_peers!, comm_info
+       resample!, mean_pose, weights, particles, pf_map, pf_best_particle, to_ekf, to_particles, peer_blob, attach_peers!, peer_selftest, detach_peers!, comm_info
 
 const libslamhip = get(ENV, "SLAMHIP_LIB", joinpath(@__DIR__, "libslamhip.so"))
 # the companion library of include/slamhip_frame.h (the rigid frame change); it links against libslamhip.so and lies beside it
@@ -38,6 +38,9 @@ const libslamhip_path = get(ENV, "SLAMHIP_PATH_LIB", joinpath(@__DIR__, "libslam
 # the companion library of include/slamhip_copy.h (an EKF state copied, grown or extracted between two handles), same arrangement
 # (opened at the first copy / select / reserve! / capacity)
 const libslamhip_copy = get(ENV, "SLAMHIP_COPY_LIB", joinpath(@__DIR__, "libslamhip_copy.so"))
+# the companion library of include/slamhip_handover.h (a state handed between the particle filter and the EKF), same arrangement
+# (opened at the first to_ekf / to_particles)
+const libslamhip_handover = get(ENV, "SLAMHIP_HANDOVER_LIB", joinpath(@__DIR__, "libslamhip_handover.so"))
 
 const SLAM_OK = Cint(0)
 const SLAM_PF_HALTED = Cint(1)
@@ -927,6 +930,42 @@ function pf_best_particle(s::PFSlamState)
     check(ccall((:slam_pf_get_particle, libslamhip), Cint, (Ptr{Cvoid}, Int64, Ref{Int64}, Ref{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
                 s.handle, -1, gid, logw, pose, lm))
     gid[], logw[], pose, lm
+end
+
+# ---- a state handed between the two filters on the device (include/slamhip_handover.h) -------------------------------------------
+"""
+    to_ekf(pf, ids = nothing; max_landmarks, device = 0) -> (EKFSlamState, info)
+
+The particle filter collapsed into an EKF state (slam_pf_to_ekf): the moment-matched joint Gaussian of the particles over the pose
+and the landmarks `ids` (1-based, distinct, any order; `nothing`: every landmark seen so far, ascending), with the pose-landmark and
+landmark-landmark cross-covariances that `pf_map` does not have.  Every chosen landmark must be in use in every particle.
+`info = (W, Neff, n, N)`.  Whole filter on one rank (`world == 1`); `device` must be the filter's.  The particles are unchanged.
+"""
+function to_ekf(s::PFSlamState{T}, ids::Union{Nothing,AbstractVector} = nothing;
+                max_landmarks::Integer = max(64, 2 * (ids === nothing ? s.max_landmarks : length(ids))), device::Integer = 0) where {T}
+    dst = EKFSlamState{T}(zeros(T, 3), zeros(T, 3, 3); max_landmarks = max_landmarks, device = device)
+    idv = ids === nothing ? Ptr{Int32}(C_NULL) : (isempty(ids) ? Int32[0] : Vector{Int32}(ids))
+    info = zeros(Float64, 4)
+    check(ccall((:slam_pf_to_ekf, libslamhip_handover), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int32}, Cint, Ptr{Cdouble}),
+                handle(dst), s.handle, idv, ids === nothing ? 0 : length(ids), info))
+    dst, (W = info[1], Neff = info[2], n = Int(info[3]), N = Int(info[4]))
+end
+
+"""
+    to_particles(state, n, ids = nothing; seed = 0, max_landmarks, device = 0) -> PFSlamState
+
+A particle filter of `n` particles drawn from the EKF state (slam_ekf_to_pf): poses from the vehicle marginal, every landmark `ids`
+(`nothing`: all) its conditional given that pose, uniform weights.  Errors with SLAM_E_NOTPD when the vehicle block or a conditional
+block is not positive definite (a vehicle known exactly: `set_pose!` and `init_landmarks!`).
+"""
+function to_particles(st::EKFSlamState{T}, n::Integer, ids::Union{Nothing,AbstractVector} = nothing; seed::Integer = 0,
+                      max_landmarks::Integer = max(1, ids === nothing ? div(length(st.x) - 3, 2) : length(ids)),
+                      device::Integer = getfield(st, :device)) where {T}
+    pf = PFSlamState{T}(n, max_landmarks; seed = seed, device = device)
+    idv = ids === nothing ? Ptr{Int32}(C_NULL) : (isempty(ids) ? Int32[0] : Vector{Int32}(ids))
+    check(ccall((:slam_ekf_to_pf, libslamhip_handover), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int32}, Cint),
+                pf.handle, handle(st), idv, ids === nothing ? 0 : length(ids)))
+    pf
 end
 
 """

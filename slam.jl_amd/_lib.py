@@ -415,6 +415,43 @@ def copy_lib():
     return yl
 
 
+# ---- the seventh companion library: a state handed between FastSLAM and the EKF (include/slamhip_handover.h) ------------------
+# Same arrangement again: libslamhip_handover.so links against libslamhip.so (run path $ORIGIN), works on its handles of both
+# kinds and is opened at the first hand-over, not at import.
+HANDOVER_LIB_PATH = os.path.join(_HERE, "libslamhip_handover.so")
+
+#: every symbol include/slamhip_handover.h declares
+HANDOVER_SIGNATURES = {
+    "slam_pf_to_ekf": (C.c_int, [_h, _h, _ip, C.c_int, _dp]),
+    "slam_ekf_to_pf": (C.c_int, [_h, _h, _ip, C.c_int]),
+}
+
+_handover = None
+
+
+def handover_lib():
+    """libslamhip_handover.so, opened on first use.  No fallback: missing or unloadable is an ImportError.  Refuses SLAMHIP_LIBRARY
+    for the reason frame_lib() gives: the handles would belong to another library than the one the companion is linked against."""
+    global _handover
+    if _handover is not None:
+        return _handover
+    if os.path.abspath(LIB_PATH) != os.path.join(_HERE, "libslamhip.so"):
+        raise ImportError(f"libslamhip_handover.so is linked against {os.path.join(_HERE, 'libslamhip.so')}; the handles of "
+                          f"{LIB_PATH} (SLAMHIP_LIBRARY) cannot be passed to it")
+    if not os.path.exists(HANDOVER_LIB_PATH):
+        raise ImportError(f"{HANDOVER_LIB_PATH} is missing: build it with `make -C slam.jl_amd/csrc`.  slam.jl_amd has no CPU fallback.")
+    try:
+        hl = C.CDLL(HANDOVER_LIB_PATH)
+    except OSError as e:  # pragma: no cover - depends on the machine
+        raise ImportError(f"cannot load {HANDOVER_LIB_PATH}: {e}.  slam.jl_amd has no CPU fallback.") from e
+    for name, (res, args) in HANDOVER_SIGNATURES.items():
+        fn = getattr(hl, name)
+        fn.restype = res
+        fn.argtypes = args
+    _handover = hl
+    return hl
+
+
 def last_error() -> str:
     msg = lib.slam_last_error()
     return msg.decode("utf-8", "replace") if msg else ""

@@ -137,7 +137,8 @@ __device__ inline T wrap_pi(T a) {         // mpi_to_pi, src/common.jl:102-110: 
     return a;
 }
 
-constexpr uint32_t STREAM_PREDICT = 0, STREAM_INIT = 1;
+constexpr uint32_t STREAM_PREDICT = 0, STREAM_INIT = 1;      // (2: STREAM_RESAMPLE, the systematic-resampling offset)
+constexpr uint32_t STREAM_HANDOVER = 3;                        // slam_ekf_to_pf (handover.hip)
 
 // One landmark record of one particle (5 strided values).
 template <typename T>

@@ -381,6 +381,16 @@ class EKFSlamState(SlamState):
             raise
         return new
 
+    # -- hand-over to the particle filter (include/slamhip_handover.h) -------------------------------
+    def to_particles(self, n, seed=0, ids=None, max_landmarks=None, neff_frac=0.75):
+        """A new :class:`PFSlamState` of ``n`` particles drawn from this state on the device (slam_ekf_to_pf): poses from the
+        vehicle marginal N(x_v, P_vv), every landmark ``ids`` (1-based, distinct; None: all) as its conditional given that pose
+        -- the Rao-Blackwell factorisation FastSLAM rests on --, uniform weights.  ``max_landmarks`` is the filter's slot count
+        (default: the landmarks handed over).  NotPositiveDefinite when P_vv or a conditional block is not positive definite
+        (a vehicle known exactly: use PFShard.set_pose and init_landmarks)."""
+        from .pf import ekf_to_particles
+        return ekf_to_particles(self, n, seed=seed, ids=ids, max_landmarks=max_landmarks, neff_frac=neff_frac)
+
     def reserve(self, max_landmarks):
         """Make room for ``max_landmarks`` landmarks (nothing happens if the capacity is already that large): a new handle of
         that capacity is created, the state is copied into it on the device (slam_ekf_copy), the new handle takes the old

@@ -28,14 +28,15 @@ import sys
 
 import numpy as np
 
-from ._lib import SLAM_F32, SLAM_F64, SLAM_PF_HALTED, SLAM_PF_PEER_BLOB_BYTES, check, evidence_lib, frame_lib, lib, path_lib
-from .ekf import _obs, _small, _ptr, rigid_fit
+from ._lib import SLAM_F32, SLAM_F64, SLAM_PF_HALTED, SLAM_PF_PEER_BLOB_BYTES, check, evidence_lib, frame_lib, handover_lib, lib, path_lib
+from .ekf import EKFSlamState, _obs, _small, _ptr, rigid_fit
 
 __all__ = ["PFShard", "PFSlamState", "FastSLAM", "LandmarkEvidence", "PathHistory", "philox_uniform", "small", "shared_page", "attach_local_peers",
-           "finalise_map", "ellipse_axes", "MapSnapshot"]
+           "finalise_map", "ellipse_axes", "MapSnapshot", "particles_to_ekf", "ekf_to_particles"]
 
 _M0, _M1, _W0, _W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
 STREAM_RESAMPLE = 2
+STREAM_HANDOVER = 3                 # slam_ekf_to_pf's three normals per particle (include/slamhip_handover.h)
 
 
 def philox_uniform(step: int, stream: int, seed: int) -> float:
@@ -471,6 +472,28 @@ class PFShard:
         check(lib.slam_pf_get_particle(self._h, int(idx), C.byref(gid), C.byref(lw), _ptr(pose),
                                        _ptr(lm) if landmarks else None))
         return int(gid.value), float(lw.value), pose, lm
+
+    # -- hand-over between the two filters on the device (include/slamhip_handover.h) ------------------------
+    def to_ekf_into(self, state, ids=None):
+        """``state`` (an EKFSlamState of this dtype on this device) becomes the moment-matched joint Gaussian of this filter's
+        particles over the pose and the landmarks ``ids`` (1-based, distinct, any order; None: every landmark seen so far,
+        ascending) -- slam_pf_to_ekf: full covariance, cross terms included.  Every chosen landmark must be in use in every
+        particle.  Returns ``{"W", "neff", "n", "N"}``.  The particle set is unchanged.  Synchronises."""
+        if not isinstance(state, EKFSlamState):
+            raise TypeError("to_ekf_into needs an EKFSlamState")
+        _idv, ptr, cnt = self._ids(ids)
+        info = np.zeros(4)
+        check(handover_lib().slam_pf_to_ekf(state._h, self._h, ptr, cnt, _ptr(info)))
+        return {"W": float(info[0]), "neff": float(info[1]), "n": int(info[2]), "N": int(info[3])}
+
+    def from_ekf(self, state, ids=None):
+        """This filter's particles are drawn from the EKF state ``state`` (slam_ekf_to_pf): poses from the vehicle marginal,
+        every landmark ``ids`` (1-based, distinct; None: all) the conditional given the pose, uniform weights; one RNG step is
+        consumed.  NotPositiveDefinite when the vehicle block or a conditional block is not positive definite.  Synchronises."""
+        if not isinstance(state, EKFSlamState):
+            raise TypeError("from_ekf needs an EKFSlamState")
+        _idv, ptr, cnt = self._ids(ids)
+        check(handover_lib().slam_ekf_to_pf(self._h, state._h, ptr, cnt))
 
     # -- resampling pieces (torch tensors on this shard's device) ---------------------------------
     def logw_tensor(self):
@@ -1070,6 +1093,28 @@ class FastSLAM:
         s = self.comm.allreduce_sum(list(self.shard.mean_pose_sums()))
         return np.array([s[0], s[1], math.atan2(s[2], s[3])])       # weights are normalised: sums are means
 
+    # -- hand-over to the EKF (include/slamhip_handover.h) --------------------------------------------------------------------
+    def to_ekf(self, ids=None, max_landmarks=None):
+        """The filter collapsed into a new :class:`EKFSlamState` on the same device and of the same dtype: the moment-matched
+        joint Gaussian of the particles over the pose and the landmarks ``ids`` (None: every landmark seen so far), with the
+        pose-landmark and landmark-landmark cross-covariances the per-landmark read-out (``map``) does not have
+        (PFShard.to_ekf_into).  ``max_landmarks`` as in EKFSlamState (default max(64, 2 N)).  ``state.handover_info`` holds
+        ``{"W", "neff", "n", "N"}``.  Whole filter on one rank only."""
+        if self.comm.world != 1 or self.shard.n != self.shard.n_global:
+            raise ValueError("the hand-over supports only a filter that lives wholly on one rank")
+        sh = self.shard
+        if max_landmarks is None:
+            cnt = sh.nl if ids is None else int(np.asarray(ids).size)
+            max_landmarks = max(64, 2 * cnt)
+        st = EKFSlamState(np.zeros(3), np.zeros((3, 3)), dtype="f32" if sh.np_dtype == np.float32 else "f64",
+                          max_landmarks=int(max_landmarks), device=sh.device.index)
+        try:
+            st.handover_info = sh.to_ekf_into(st, ids)
+        except Exception:
+            st.close()
+            raise
+        return st
+
     # -- the map ---------------------------------------------------------------------------------------------------------
     def map_sums(self, ids=None):
         """The filter's sums of the weighted map (PFShard.map_sums added over the ranks), [1 + cnt, 10]."""
@@ -1275,6 +1320,25 @@ class PFSlamState(FastSLAM):
                 print(f"[close rank {dist.get_rank()}] destroy", file=sys.stderr, flush=True)
             self.peers = False
         self.shard.close()
+
+
+def particles_to_ekf(pf, ids=None, max_landmarks=None):
+    """``pf.to_ekf(ids, max_landmarks)`` as a free function (the reference's style)."""
+    return pf.to_ekf(ids, max_landmarks)
+
+
+def ekf_to_particles(state, n, seed=0, ids=None, max_landmarks=None, neff_frac=0.75):
+    """``state.to_particles(n, ...)`` as a free function: a :class:`PFSlamState` of ``n`` particles drawn from the EKF state
+    (vehicle marginal, landmark conditionals), on its device and of its dtype."""
+    cnt = state.N if ids is None else int(np.asarray(ids).size)
+    pf = PFSlamState(int(n), int(max_landmarks) if max_landmarks is not None else max(cnt, 1), seed=seed,
+                     dtype="f32" if state.np_dtype == np.float32 else "f64", device=state.device, neff_frac=neff_frac, distributed=False)
+    try:
+        pf.shard.from_ekf(state, ids)
+    except Exception:
+        pf.close()
+        raise
+    return pf
 
 
 def attach_local_peers(shards):
