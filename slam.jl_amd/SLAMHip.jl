@@ -17,7 +17,8 @@ export SlamState, EKFSlamState, set_state!, predict, update, add_features, assoc
        ekf_predict!, ekf_update!, augment!, observe!, cov_block, cov_diag, landmark_blocks, gate_mode!, gate_info, state_written!, remove_features!, find_duplicates, merge_landmarks!, transform!, join!, submap, select, reserve!, capacity, associate_joint, observe_joint!, joint_nis, chi2_table, feature_ellipses, vehicle_ellipse,
        PFSlamState, set_pose!, init_landmarks!, pf_predict!, update_known!, step!, step_async!, step_async_batch!, step_unknown!, LandmarkEvidence, evidence_update!, counters, step_unknown_pruned!, flush!,
        PathHistory, record!, path_info, path_record, trace, best_path, mean_path, survivors,
-       resample!, mean_pose, weights, particles, pf_map, pf_best_particle, to_ekf, to_particles, peer_blob, attach_peers!, peer_selftest, detach_peers!, comm_info
+       resample!, mean_pose, weights, particles, pf_map, pf_best_particle, to_ekf, to_particles, peer_blob, attach_peers!, peer_selftest, detach_peers!, comm_info,
+       upload!, resize, pose_bins, kld_particle_count, pf_meta
 
 const libslamhip = get(ENV, "SLAMHIP_LIB", joinpath(@__DIR__, "libslamhip.so"))
 # the companion library of include/slamhip_frame.h (the rigid frame change); it links against libslamhip.so and lies beside it
@@ -41,6 +42,10 @@ const libslamhip_copy = get(ENV, "SLAMHIP_COPY_LIB", joinpath(@__DIR__, "libslam
 # the companion library of include/slamhip_handover.h (a state handed between the particle filter and the EKF), same arrangement
 # (opened at the first to_ekf / to_particles)
 const libslamhip_handover = get(ENV, "SLAMHIP_HANDOVER_LIB", joinpath(@__DIR__, "libslamhip_handover.so"))
+
+# the companion library of include/slamhip_pfcopy.h (a particle set uploaded, copied, selected and resized between handles), same
+# arrangement (opened at the first copy / select / resize / reserve! / upload! / pose_bins of a particle filter)
+const libslamhip_pfcopy = get(ENV, "SLAMHIP_PFCOPY_LIB", joinpath(@__DIR__, "libslamhip_pfcopy.so"))
 
 const SLAM_OK = Cint(0)
 const SLAM_PF_HALTED = Cint(1)
@@ -966,6 +971,120 @@ function to_particles(st::EKFSlamState{T}, n::Integer, ids::Union{Nothing,Abstra
     check(ccall((:slam_ekf_to_pf, libslamhip_handover), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int32}, Cint),
                 pf.handle, handle(st), idv, ids === nothing ? 0 : length(ids)))
     pf
+end
+
+# ---- a particle set moved on the device (include/slamhip_pfcopy.h) -------------------------------------------------------------
+"(n_local, n_global, first_id, max_landmarks, dtype, RNG step, resample count, seed) and the per-landmark `seen` flags."
+function pf_meta(s::PFSlamState)
+    out = zeros(Int64, 8)
+    seen = zeros(UInt8, s.max_landmarks)
+    check(ccall((:slam_pf_get_meta, libslamhip_pfcopy), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{UInt8}), s.handle, out, seen))
+    out, seen
+end
+
+pf_one_rank(s::PFSlamState) = s.world == 1 || error("only a filter that lives wholly on one rank can be copied, selected or resized")
+
+"""
+    copy!(dst, src; fill = 0) -> dst
+
+`dst` becomes `src` bit for bit (slam_pf_copy): poses, log-weights as `particles(src)` returns them, every landmark record -- read
+where lazy resampling left it, `src` is only read --, the RNG state and the resample count.  Equal particle counts,
+`dst.max_landmarks >= src.max_landmarks`; the slots beyond follow `fill` (0: as created, 1: unused, for unknown correspondences).
+"""
+function Base.copy!(dst::PFSlamState{T}, src::PFSlamState{T}; fill::Integer = 0) where {T}
+    pf_one_rank(dst); pf_one_rank(src)
+    check(ccall((:slam_pf_copy, libslamhip_pfcopy), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint), dst.handle, src.handle, fill))
+    dst
+end
+
+"A second filter equal to `s` bit for bit; driven like `s` it stays equal to it.  `max_landmarks` may be larger than `s`'s."
+function Base.copy(s::PFSlamState{T}; max_landmarks::Integer = s.max_landmarks, fill::Integer = 0, device::Integer = 0) where {T}
+    pf_one_rank(s)
+    copy!(PFSlamState{T}(s.n, max_landmarks; device = device), s; fill = fill)
+end
+
+"A new filter whose landmark k is slot `ids[k]` of `s` (1-based, distinct, any order) -- slam_pf_select."
+function select(s::PFSlamState{T}, ids::AbstractVector{<:Integer}; max_landmarks::Integer = max(1, length(ids)), fill::Integer = 0,
+                device::Integer = 0) where {T}
+    pf_one_rank(s)
+    dst = PFSlamState{T}(s.n, max_landmarks; device = device)
+    idv = isempty(ids) ? Int32[0] : Vector{Int32}(ids)
+    check(ccall((:slam_pf_select, libslamhip_pfcopy), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int32}, Cint, Cint),
+                dst.handle, s.handle, idv, length(ids), fill))
+    dst
+end
+
+"""
+    resize(s, n, gmax, u0; fill = 0) -> (PFSlamState, ancestors)
+
+A new filter of `n` particles drawn from `s`'s by systematic resampling into `n` slots (slam_pf_resize): uniform weights, the
+resample count is `s`'s plus one, `s` is only read.  `gmax`: the largest (normalised) log-weight of `s`; `u0` in [0, 1).
+"""
+function resize(s::PFSlamState{T}, n::Integer, gmax::Real, u0::Real; fill::Integer = 0, device::Integer = 0) where {T}
+    pf_one_rank(s)
+    dst = PFSlamState{T}(n, s.max_landmarks; device = device)
+    anc = zeros(Int32, n)
+    check(ccall((:slam_pf_resize, libslamhip_pfcopy), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cdouble, Cdouble, Cint, Ptr{Int32}),
+                dst.handle, s.handle, gmax, u0, fill, anc))
+    dst, anc
+end
+
+"""
+    reserve!(s, max_landmarks; unknown = false) -> s
+
+Make room for `max_landmarks` landmark slots: a new handle is created, the particles are copied into it on the device, it takes
+the old handle's place inside `s` and the old one is destroyed.  `unknown`: the new slots are unused records, as a filter with
+unknown correspondences needs them.  Objects that borrow the old handle (PathHistory, LandmarkEvidence) must be gone before.
+"""
+function reserve!(s::PFSlamState{T}, max_landmarks::Integer; unknown::Bool = false, device::Integer = 0) where {T}
+    pf_one_rank(s)
+    max_landmarks <= s.max_landmarks && return s
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:slam_pf_create, libslamhip), Cint, (Ref{Ptr{Cvoid}}, Cint, Int64, Int64, Int64, Cint, Cint, UInt64),
+                h, T === Float32 ? SLAM_F32 : SLAM_F64, s.n, s.n, 0, max_landmarks, device, 0))
+    rc = ccall((:slam_pf_copy, libslamhip_pfcopy), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint), h[], s.handle, unknown ? 1 : 0)
+    if rc != SLAM_OK
+        ccall((:slam_pf_destroy, libslamhip), Cint, (Ptr{Cvoid},), h[])
+        check(rc)
+    end
+    old = s.handle
+    s.handle = h[]
+    s.max_landmarks = max_landmarks
+    ccall((:slam_pf_destroy, libslamhip), Cint, (Ptr{Cvoid},), old)
+    s
+end
+
+"""
+    upload!(s; pose = nothing, logw = nothing, lm = nothing, seen = nothing) -> s
+
+The inverse of `particles` (slam_pf_upload): `pose` n x 3, `logw` n, `lm` n x 5 x max_landmarks in the filter's element type, `seen`
+one flag per landmark; `lm` and `seen` go together.  The values are stored as given.
+"""
+function upload!(s::PFSlamState{T}; pose = nothing, logw = nothing, lm = nothing, seen = nothing) where {T}
+    (lm === nothing) == (seen === nothing) || error("lm and seen are given together or not at all")
+    p = pose === nothing ? Ptr{Cvoid}(C_NULL) : Matrix{T}(pose)
+    w = logw === nothing ? Ptr{Cvoid}(C_NULL) : Vector{T}(logw)
+    l = lm === nothing ? Ptr{Cvoid}(C_NULL) : Array{T,3}(lm)
+    f = seen === nothing ? Ptr{UInt8}(C_NULL) : Vector{UInt8}(seen .!= 0)
+    pose === nothing || size(p) == (s.n, 3) || error("pose must be n x 3")
+    logw === nothing || length(w) == s.n || error("logw must have n entries")
+    lm === nothing || (size(l) == (s.n, 5, s.max_landmarks) && length(f) == s.max_landmarks) || error("lm must be n x 5 x max_landmarks")
+    check(ccall((:slam_pf_upload, libslamhip_pfcopy), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{UInt8}), s.handle, p, w, l, f))
+    s
+end
+
+"The number of distinct occupied cells of the pose histogram (slam_pf_pose_bins): the k of KLD-sampling."
+function pose_bins(s::PFSlamState, cell_xy::Real, cell_phi::Real)
+    out = Ref{Int64}(0)
+    check(ccall((:slam_pf_pose_bins, libslamhip_pfcopy), Cint, (Ptr{Cvoid}, Cdouble, Cdouble, Ref{Int64}), s.handle, cell_xy, cell_phi, out))
+    out[]
+end
+
+"The particle count KLD-sampling (Fox 2003) asks for at `k` occupied cells, clamped to [n_min, n_max]; `n_min` for k < 2."
+function kld_particle_count(k::Integer; eps::Real = 0.05, z::Real = 2.326, n_min::Integer = 64, n_max::Integer = 1 << 22)
+    k < 2 && return Int(n_min)
+    a = 2.0 / (9.0 * (k - 1))
+    clamp(ceil(Int, (k - 1) / (2.0 * eps) * (1.0 - a + sqrt(a) * z)^3), Int(n_min), Int(n_max))
 end
 
 """

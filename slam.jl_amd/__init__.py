@@ -17,6 +17,6 @@ from .ekf import (DeviceRef, EKFSlamState, SlamState, add_features, associate, a
                   rigid_fit, transform_features, transform_features_,
                   copy_state, select_features, select_map, grown_capacity)
 from .pf import (FastSLAM, LandmarkEvidence, PathHistory, PFShard, PFSlamState, TorchComm, attach_local_peers, philox_uniform, shared_page,  # noqa: F401
-                 small, particles_to_ekf, ekf_to_particles)
+                 small, particles_to_ekf, ekf_to_particles, save_particles, load_particles, kld_particle_count)
 from . import sim  # noqa: F401
 from . import telemetry  # noqa: F401

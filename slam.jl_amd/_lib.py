@@ -452,6 +452,48 @@ def handover_lib():
     return hl
 
 
+# ---- the eighth companion library: a particle set uploaded, copied, selected and resized (include/slamhip_pfcopy.h) ------------
+# Same arrangement again: libslamhip_pfcopy.so links against libslamhip.so (run path $ORIGIN), works on its particle-filter
+# handles and is opened at the first call, not at import.
+PFCOPY_LIB_PATH = os.path.join(_HERE, "libslamhip_pfcopy.so")
+
+#: every symbol include/slamhip_pfcopy.h declares
+PFCOPY_SIGNATURES = {
+    "slam_pf_get_meta": (C.c_int, [_h, _i64p, C.c_void_p]),
+    "slam_pf_set_rng": (C.c_int, [_h, C.c_uint64, C.c_uint32]),
+    "slam_pf_upload": (C.c_int, [_h, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "slam_pf_select": (C.c_int, [_h, _h, _ip, C.c_int, C.c_int]),
+    "slam_pf_copy": (C.c_int, [_h, _h, C.c_int]),
+    "slam_pf_resize": (C.c_int, [_h, _h, C.c_double, C.c_double, C.c_int, _ip]),
+    "slam_pf_pose_bins": (C.c_int, [_h, C.c_double, C.c_double, _i64p]),
+}
+
+_pfcopy = None
+
+
+def pfcopy_lib():
+    """libslamhip_pfcopy.so, opened on first use.  No fallback: missing or unloadable is an ImportError.  Refuses SLAMHIP_LIBRARY
+    for the reason frame_lib() gives: the handles would belong to another library than the one the companion is linked against."""
+    global _pfcopy
+    if _pfcopy is not None:
+        return _pfcopy
+    if os.path.abspath(LIB_PATH) != os.path.join(_HERE, "libslamhip.so"):
+        raise ImportError(f"libslamhip_pfcopy.so is linked against {os.path.join(_HERE, 'libslamhip.so')}; the handles of "
+                          f"{LIB_PATH} (SLAMHIP_LIBRARY) cannot be passed to it")
+    if not os.path.exists(PFCOPY_LIB_PATH):
+        raise ImportError(f"{PFCOPY_LIB_PATH} is missing: build it with `make -C slam.jl_amd/csrc`.  slam.jl_amd has no CPU fallback.")
+    try:
+        kl = C.CDLL(PFCOPY_LIB_PATH)
+    except OSError as e:  # pragma: no cover - depends on the machine
+        raise ImportError(f"cannot load {PFCOPY_LIB_PATH}: {e}.  slam.jl_amd has no CPU fallback.") from e
+    for name, (res, args) in PFCOPY_SIGNATURES.items():
+        fn = getattr(kl, name)
+        fn.restype = res
+        fn.argtypes = args
+    _pfcopy = kl
+    return kl
+
+
 def last_error() -> str:
     msg = lib.slam_last_error()
     return msg.decode("utf-8", "replace") if msg else ""

@@ -28,11 +28,12 @@ import sys
 
 import numpy as np
 
-from ._lib import SLAM_F32, SLAM_F64, SLAM_PF_HALTED, SLAM_PF_PEER_BLOB_BYTES, check, evidence_lib, frame_lib, handover_lib, lib, path_lib
+from ._lib import SLAM_F32, SLAM_F64, SLAM_PF_HALTED, SLAM_PF_PEER_BLOB_BYTES, check, evidence_lib, frame_lib, handover_lib, lib, path_lib, pfcopy_lib
 from .ekf import EKFSlamState, _obs, _small, _ptr, rigid_fit
 
 __all__ = ["PFShard", "PFSlamState", "FastSLAM", "LandmarkEvidence", "PathHistory", "philox_uniform", "small", "shared_page", "attach_local_peers",
-           "finalise_map", "ellipse_axes", "MapSnapshot", "particles_to_ekf", "ekf_to_particles"]
+           "finalise_map", "ellipse_axes", "MapSnapshot", "particles_to_ekf", "ekf_to_particles", "save_particles", "load_particles",
+           "kld_particle_count"]
 
 _M0, _M1, _W0, _W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
 STREAM_RESAMPLE = 2
@@ -150,6 +151,7 @@ class PFShard:
         rows = C.c_int()
         check(lib.slam_pf_record_rows(self._h, C.byref(rows)))
         self.rows = rows.value
+        self._borrowers = 0                          # LandmarkEvidence / PathHistory objects that follow this shard's particles
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
@@ -495,6 +497,73 @@ class PFShard:
         _idv, ptr, cnt = self._ids(ids)
         check(handover_lib().slam_ekf_to_pf(self._h, state._h, ptr, cnt))
 
+    # -- the particle set moved on the device (include/slamhip_pfcopy.h) ------------------------------------
+    def meta(self):
+        """slam_pf_get_meta: ``{"n", "n_global", "first", "max_landmarks", "dtype", "step", "resamples", "seed", "seen"}`` with
+        ``seen`` the per-landmark flags as a uint8 array.  Waits for the queue of an auto-mode filter."""
+        out = np.zeros(8, dtype=np.int64)
+        seen = np.zeros(self.nl, dtype=np.uint8)
+        check(pfcopy_lib().slam_pf_get_meta(self._h, _ptr(out, C.c_int64), seen.ctypes.data))
+        return {"n": int(out[0]), "n_global": int(out[1]), "first": int(out[2]), "max_landmarks": int(out[3]),
+                "dtype": "f32" if int(out[4]) == SLAM_F32 else "f64", "step": int(out[5]), "resamples": int(out[6]),
+                "seed": int(out[7]) & 0xFFFFFFFFFFFFFFFF, "seen": seen}
+
+    def set_rng(self, seed, step):
+        """The Philox key and the step counter (slam_pf_set_rng)."""
+        check(pfcopy_lib().slam_pf_set_rng(self._h, C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_uint32(int(step))))
+        self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+
+    def upload(self, pose=None, logw=None, lm=None, seen=None):
+        """The inverse of :meth:`download` (slam_pf_upload): ``pose`` [3, n], ``logw`` [n], ``lm`` [nl, 5, n] in the shard's dtype
+        and ``seen`` [nl] flags; ``pose`` and ``logw`` may each be None (that part stays), ``lm`` and ``seen`` go together.  The
+        values are stored as given; with ``lm`` the maps are plain afterwards.  Synchronises."""
+        def arr(a, shape):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=self.np_dtype)
+            if a.shape != shape:
+                raise ValueError(f"expected an array of shape {shape}, got {a.shape}")
+            return a
+        if (lm is None) != (seen is None):
+            raise ValueError("lm and seen are given together or not at all")
+        pose, logw, lm = arr(pose, (3, self.n)), arr(logw, (self.n,)), arr(lm, (self.nl, 5, self.n))
+        sn = None
+        if seen is not None:
+            sn = np.ascontiguousarray(np.asarray(seen).reshape(-1) != 0, dtype=np.uint8)
+            if sn.shape != (self.nl,):
+                raise ValueError(f"expected {self.nl} seen flags")
+        check(pfcopy_lib().slam_pf_upload(self._h, None if pose is None else pose.ctypes.data, None if logw is None else logw.ctypes.data,
+                                          None if lm is None else lm.ctypes.data, None if sn is None else sn.ctypes.data))
+
+    def copy_from(self, src, fill=0):
+        """This shard becomes a copy of ``src`` (slam_pf_copy): poses, log-weights as ``src.download()`` returns them, every
+        record bit for bit -- read where lazy resampling left it, ``src`` is only read --, the RNG state and the resample
+        count.  Slots beyond ``src.nl`` follow ``fill`` (0: as created, 1: unused, for unknown correspondences)."""
+        check(pfcopy_lib().slam_pf_copy(self._h, src._h, int(fill)))
+        self.seed = src.seed
+
+    def select_from(self, src, ids, fill=0):
+        """As :meth:`copy_from` with landmark k of this shard = slot ``ids[k - 1]`` of ``src`` (1-based, distinct, any order;
+        None: all) -- slam_pf_select."""
+        _idv, ptr, cnt = self._ids(ids)
+        check(pfcopy_lib().slam_pf_select(self._h, src._h, ptr, cnt, int(fill)))
+        self.seed = src.seed
+
+    def resize_from(self, src, gmax, u0, fill=0):
+        """This shard's n particles are drawn from ``src``'s by systematic resampling into n slots (slam_pf_resize; the counts
+        may differ): uniform weights, the resample count is ``src``'s plus one.  ``gmax``: the largest (normalised) log-weight
+        of ``src``.  Returns the ancestor table, int32 [n]."""
+        anc = np.empty(self.n, dtype=np.int32)
+        check(pfcopy_lib().slam_pf_resize(self._h, src._h, float(gmax), float(u0), int(fill), _ptr(anc, C.c_int32)))
+        self.seed = src.seed
+        return anc
+
+    def pose_bins(self, cell_xy, cell_phi):
+        """The number of distinct occupied cells of the pose histogram (slam_pf_pose_bins): the k of KLD-sampling."""
+        out = C.c_int64()
+        check(pfcopy_lib().slam_pf_pose_bins(self._h, float(cell_xy), float(cell_phi), C.byref(out)))
+        return int(out.value)
+
     # -- resampling pieces (torch tensors on this shard's device) ---------------------------------
     def logw_tensor(self):
         import torch
@@ -579,12 +648,14 @@ class LandmarkEvidence:
         self._e = C.c_void_p()
         self._lib = evidence_lib()
         check(self._lib.slam_pf_evidence_create(C.byref(self._e), shard._h))
+        shard._borrowers = getattr(shard, "_borrowers", 0) + 1
 
     def close(self):
         if getattr(self, "_e", None) is not None and self._e:
             if self.shard._h:                       # (a shard closed first took the stream along: nothing left to free on)
                 self._lib.slam_pf_evidence_destroy(self._e)
             self._e = C.c_void_p()
+            self.shard._borrowers = getattr(self.shard, "_borrowers", 1) - 1
 
     def __del__(self):
         try:
@@ -652,12 +723,14 @@ class PathHistory:
         self._p = C.c_void_p()
         self._lib = path_lib()
         check(self._lib.slam_pf_path_create(C.byref(self._p), shard._h, self.cap))
+        shard._borrowers = getattr(shard, "_borrowers", 0) + 1
 
     def close(self):
         if getattr(self, "_p", None) is not None and self._p:
             if self.shard._h:                       # (a shard closed first took the stream along: nothing left to free on)
                 self._lib.slam_pf_path_destroy(self._p)
             self._p = C.c_void_p()
+            self.shard._borrowers = getattr(self.shard, "_borrowers", 1) - 1
 
     def __del__(self):
         try:
@@ -1115,6 +1188,88 @@ class FastSLAM:
             raise
         return st
 
+    # -- clone, more landmark slots, another particle count (include/slamhip_pfcopy.h) ------------------------------------------
+    def _movable(self, what):
+        sh = self.shard
+        if self.comm.world != 1 or not isinstance(self.comm, _SingleProcess):
+            raise ValueError(f"{what} supports only a filter without a comm, wholly on one rank")
+        if sh.n != sh.n_global or sh.first != 0 or getattr(self, "peers", False):
+            raise ValueError(f"{what} supports only a filter that lives wholly on one shard, without peers")
+        if self.path_history is not None or getattr(sh, "_borrowers", 0):
+            raise ValueError(f"{what}: a PathHistory or LandmarkEvidence object follows this filter's particles; such histories "
+                             "are not copied -- close it first")
+
+    def _new_shard(self, n, max_landmarks):
+        sh = self.shard
+        return PFShard(int(n), int(max_landmarks), sh.seed, dtype="f32" if sh.np_dtype == np.float32 else "f64", device=sh.device.index)
+
+    def _adopt(self, shard):
+        old, self.shard = self.shard, shard
+        old.close()
+        if hasattr(self, "n"):
+            self.n = shard.n
+
+    def clone(self):
+        """A second filter equal to this one bit for bit -- particles, RNG state, resample count -- on the same device
+        (PFShard.copy_from: this filter is only read).  Driven like the original it stays equal to it."""
+        self._movable("clone")
+        new = object.__new__(type(self))
+        FastSLAM.__init__(new, self._new_shard(self.shard.n, self.shard.nl), None, self.neff_frac)
+        for name in ("n", "peers", "selftest_ok"):
+            if hasattr(self, name):
+                setattr(new, name, getattr(self, name))
+        try:
+            new.shard.copy_from(self.shard)
+        except Exception:
+            new.shard.close()
+            raise
+        new.fused, new.resamples, new.last_neff, new._gmax_norm = self.fused, self.resamples, self.last_neff, self._gmax_norm
+        return new
+
+    def reserve(self, max_landmarks, unknown=False):
+        """Give the filter ``max_landmarks`` >= the current landmark slots, in place: the particles move to a new shard on the
+        device (PFShard.copy_from) and the old one is closed.  ``unknown``: the new slots are unused records, as a filter
+        with unknown correspondences needs them; otherwise they are as a new filter has them."""
+        self._movable("reserve")
+        if int(max_landmarks) < self.shard.nl:
+            raise ValueError("reserve cannot drop landmark slots (PFShard.select_from chooses landmarks)")
+        new = self._new_shard(self.shard.n, max_landmarks)
+        try:
+            new.copy_from(self.shard, fill=1 if unknown else 0)
+        except Exception:
+            new.close()
+            raise
+        self._adopt(new)
+
+    def resize(self, n):
+        """The filter continues with ``n`` particles, in place: drawn from the current ones by systematic resampling into n
+        slots (PFShard.resize_from), uniform weights, counted as a resampling; the offset is the one an ordinary resampling
+        would take now.  Normalises first when the weights are not.  Returns the ancestor table."""
+        self._movable("resize")
+        if self._gmax_norm is None:
+            self.normalize()
+        new = self._new_shard(n, self.shard.nl)
+        try:
+            anc = new.resize_from(self.shard, self._gmax_norm, philox_uniform(self.resamples, STREAM_RESAMPLE, self.shard.seed))
+        except Exception:
+            new.close()
+            raise
+        self._adopt(new)
+        self._gmax_norm = None
+        self.resamples += 1
+        self.last_neff = float(n)
+        return anc
+
+    def adapt(self, cell_xy, cell_phi, eps=0.05, z=2.326, n_min=64, n_max=1 << 22):
+        """KLD-sampling (Fox 2003) between steps: count the occupied cells of the pose histogram (PFShard.pose_bins), take
+        the particle count they ask for (:func:`kld_particle_count`) and :meth:`resize` when it differs from the current
+        one.  Returns the count the filter continues with."""
+        self._movable("adapt")
+        want = kld_particle_count(self.shard.pose_bins(cell_xy, cell_phi), eps=eps, z=z, n_min=n_min, n_max=n_max)
+        if want != self.shard.n:
+            self.resize(want)
+        return want
+
     # -- the map ---------------------------------------------------------------------------------------------------------
     def map_sums(self, ids=None):
         """The filter's sums of the weighted map (PFShard.map_sums added over the ranks), [1 + cnt, 10]."""
@@ -1339,6 +1494,41 @@ def ekf_to_particles(state, n, seed=0, ids=None, max_landmarks=None, neff_frac=0
         pf.close()
         raise
     return pf
+
+
+def save_particles(shard):
+    """A checkpoint of a :class:`PFShard` as a dict of NumPy arrays and scalars: ``pose``, ``logw``, ``lm`` (what ``download``
+    returns), ``seen`` and the meta (sizes, dtype, seed, RNG step, resample count).  :func:`load_particles` restores it."""
+    pose, logw, lm = shard.download()
+    d = shard.meta()                                # (after the download: an auto-mode filter has been left by then)
+    d.update(pose=pose, logw=logw, lm=lm)
+    return d
+
+
+def load_particles(d, device=0):
+    """A new :class:`PFShard` from a :func:`save_particles` dict: same particles, RNG state and resample count, so that the
+    restored filter continues bit for bit like the saved one."""
+    sh = PFShard(d["n"], d["max_landmarks"], d["seed"], dtype=d["dtype"], first=d["first"], n_global=d["n_global"], device=device)
+    try:
+        sh.upload(d["pose"], d["logw"], d["lm"], d["seen"])
+        sh.set_rng(d["seed"], d["step"])
+        sh.set_resample_count(d["resamples"])
+    except Exception:
+        sh.close()
+        raise
+    return sh
+
+
+def kld_particle_count(k, eps=0.05, z=2.326, n_min=64, n_max=1 << 22):
+    """The particle count KLD-sampling (Fox 2003) asks for when the pose histogram has ``k`` occupied cells: with a = 2 / (9 (k - 1)),
+    ceil((k - 1) / (2 eps) * (1 - a + sqrt(a) z)^3), clamped to [n_min, n_max]; ``n_min`` for k < 2.  ``eps``: the bound on the
+    K-L distance, ``z``: the upper 1 - delta quantile of the standard normal (2.326: delta = 0.01).  Host arithmetic."""
+    k = int(k)
+    if k < 2:
+        return int(n_min)
+    a = 2.0 / (9.0 * (k - 1))
+    n = math.ceil((k - 1) / (2.0 * float(eps)) * (1.0 - a + math.sqrt(a) * float(z)) ** 3)
+    return int(min(max(n, int(n_min)), int(n_max)))
 
 
 def attach_local_peers(shards):
