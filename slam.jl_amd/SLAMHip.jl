@@ -18,7 +18,7 @@ export SlamState, EKFSlamState, set_state!, predict, update, add_features, assoc
        PFSlamState, set_pose!, init_landmarks!, pf_predict!, update_known!, step!, step_async!, step_async_batch!, step_unknown!, LandmarkEvidence, evidence_update!, counters, step_unknown_pruned!, flush!,
        PathHistory, record!, path_info, path_record, trace, best_path, mean_path, survivors,
        resample!, mean_pose, weights, particles, pf_map, pf_best_particle, to_ekf, to_particles, peer_blob, attach_peers!, peer_selftest, detach_peers!, comm_info,
-       upload!, resize, pose_bins, kld_particle_count, pf_meta
+       upload!, resize, pose_bins, kld_particle_count, pf_meta, set_rng!
 
 const libslamhip = get(ENV, "SLAMHIP_LIB", joinpath(@__DIR__, "libslamhip.so"))
 # the companion library of include/slamhip_frame.h (the rigid frame change); it links against libslamhip.so and lies beside it
@@ -980,6 +980,12 @@ function pf_meta(s::PFSlamState)
     seen = zeros(UInt8, s.max_landmarks)
     check(ccall((:slam_pf_get_meta, libslamhip_pfcopy), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{UInt8}), s.handle, out, seen))
     out, seen
+end
+
+"The Philox key and the step counter (slam_pf_set_rng): with `pf_meta` and `upload!`, what completes a checkpoint."
+function set_rng!(s::PFSlamState, seed::Integer, step::Integer)
+    check(ccall((:slam_pf_set_rng, libslamhip_pfcopy), Cint, (Ptr{Cvoid}, UInt64, UInt32), s.handle, seed % UInt64, step))
+    s
 end
 
 pf_one_rank(s::PFSlamState) = s.world == 1 || error("only a filter that lives wholly on one rank can be copied, selected or resized")

@@ -166,85 +166,61 @@ for _name, (_res, _args) in SIGNATURES.items():
     _fn.argtypes = _args
 
 
-# ---- the companion library: the rigid frame change (include/slamhip_frame.h) -----------------------------------------------
-# libslamhip.so exports exactly what its two headers declare; the frame change lives beside it in libslamhip_frame.so, which
-# links against libslamhip.so (run path $ORIGIN) and works on its handles.  It is opened at the first transform, not at
-# import: a tree with only libslamhip.so built imports and runs as before.
-FRAME_LIB_PATH = os.path.join(_HERE, "libslamhip_frame.so")
+# ---- the companion libraries ------------------------------------------------------------------------------------------------
+# libslamhip.so exports exactly what its two headers declare; every later feature lives beside it in a companion library
+# libslamhip_<name>.so, which links against libslamhip.so (run path $ORIGIN), works on its handles and exports what
+# include/slamhip_<name>.h declares.  A companion is opened at its first use, not at import: a tree with only libslamhip.so
+# built imports and runs as before.
+class Companion:
+    """libslamhip_<name>.so beside the package and its signature table; calling it returns the library, opened on first use.
+    No fallback: missing or unloadable is an ImportError.  With SLAMHIP_LIBRARY pointing elsewhere the handles belong to THAT
+    library while the companion is linked against libslamhip.so, whose copy of the helpers it would run on them: refused."""
 
+    def __init__(self, name, signatures):
+        self.name = name
+        self.path = os.path.join(_HERE, f"libslamhip_{name}.so")
+        self.signatures = signatures
+        self._lib = None
+
+    def __call__(self):
+        if self._lib is not None:
+            return self._lib
+        soname = os.path.basename(self.path)
+        if os.path.abspath(LIB_PATH) != os.path.join(_HERE, "libslamhip.so"):
+            raise ImportError(f"{soname} is linked against {os.path.join(_HERE, 'libslamhip.so')}; the handles of "
+                              f"{LIB_PATH} (SLAMHIP_LIBRARY) cannot be passed to it")
+        if not os.path.exists(self.path):
+            raise ImportError(f"{self.path} is missing: build it with `make -C slam.jl_amd/csrc`.  slam.jl_amd has no CPU fallback.")
+        try:
+            cl = C.CDLL(self.path)
+        except OSError as e:  # pragma: no cover - depends on the machine
+            raise ImportError(f"cannot load {self.path}: {e}.  slam.jl_amd has no CPU fallback.") from e
+        for name, (res, args) in self.signatures.items():
+            fn = getattr(cl, name)
+            fn.restype = res
+            fn.argtypes = args
+        self._lib = cl
+        return cl
+
+
+# ---- frame: the rigid frame change, opened at the first transform -----------------------------------------------------------
 #: every symbol include/slamhip_frame.h declares
 FRAME_SIGNATURES = {
     "slam_ekf_transform": (C.c_int, [_h, C.c_double, C.c_double, C.c_double]),
     "slam_pf_transform": (C.c_int, [_h, C.c_double, C.c_double, C.c_double]),
 }
+frame_lib = Companion("frame", FRAME_SIGNATURES)
+FRAME_LIB_PATH = frame_lib.path
 
-_frame = None
-
-
-def frame_lib():
-    """libslamhip_frame.so, opened on first use.  No fallback: missing or unloadable is an ImportError.  With SLAMHIP_LIBRARY
-    pointing elsewhere the handles belong to THAT library while the companion is linked against libslamhip.so, whose copy
-    of the helpers it would run on them: refused."""
-    global _frame
-    if _frame is not None:
-        return _frame
-    if os.path.abspath(LIB_PATH) != os.path.join(_HERE, "libslamhip.so"):
-        raise ImportError(f"libslamhip_frame.so is linked against {os.path.join(_HERE, 'libslamhip.so')}; the handles of "
-                          f"{LIB_PATH} (SLAMHIP_LIBRARY) cannot be passed to it")
-    if not os.path.exists(FRAME_LIB_PATH):
-        raise ImportError(f"{FRAME_LIB_PATH} is missing: build it with `make -C slam.jl_amd/csrc`.  slam.jl_amd has no CPU fallback.")
-    try:
-        fl = C.CDLL(FRAME_LIB_PATH)
-    except OSError as e:  # pragma: no cover - depends on the machine
-        raise ImportError(f"cannot load {FRAME_LIB_PATH}: {e}.  slam.jl_amd has no CPU fallback.") from e
-    for name, (res, args) in FRAME_SIGNATURES.items():
-        fn = getattr(fl, name)
-        fn.restype = res
-        fn.argtypes = args
-    _frame = fl
-    return fl
-
-
-# ---- the second companion library: map joining (include/slamhip_join.h) ------------------------------------------------------
-# Same arrangement as the frame change: libslamhip_join.so links against libslamhip.so (run path $ORIGIN), works on its handles
-# and is opened at the first join, not at import.
-JOIN_LIB_PATH = os.path.join(_HERE, "libslamhip_join.so")
-
+# ---- join: map joining, opened at the first join ------------------------------------------------------------------------------
 #: every symbol include/slamhip_join.h declares
 JOIN_SIGNATURES = {
     "slam_ekf_join": (C.c_int, [_h, _h, _ip]),
 }
+join_lib = Companion("join", JOIN_SIGNATURES)
+JOIN_LIB_PATH = join_lib.path
 
-_join = None
-
-
-def join_lib():
-    """libslamhip_join.so, opened on first use.  No fallback: missing or unloadable is an ImportError.  Refuses SLAMHIP_LIBRARY
-    for the reason frame_lib() gives: the handles would belong to another library than the one the companion is linked against."""
-    global _join
-    if _join is not None:
-        return _join
-    if os.path.abspath(LIB_PATH) != os.path.join(_HERE, "libslamhip.so"):
-        raise ImportError(f"libslamhip_join.so is linked against {os.path.join(_HERE, 'libslamhip.so')}; the handles of "
-                          f"{LIB_PATH} (SLAMHIP_LIBRARY) cannot be passed to it")
-    if not os.path.exists(JOIN_LIB_PATH):
-        raise ImportError(f"{JOIN_LIB_PATH} is missing: build it with `make -C slam.jl_amd/csrc`.  slam.jl_amd has no CPU fallback.")
-    try:
-        jl = C.CDLL(JOIN_LIB_PATH)
-    except OSError as e:  # pragma: no cover - depends on the machine
-        raise ImportError(f"cannot load {JOIN_LIB_PATH}: {e}.  slam.jl_amd has no CPU fallback.") from e
-    for name, (res, args) in JOIN_SIGNATURES.items():
-        fn = getattr(jl, name)
-        fn.restype = res
-        fn.argtypes = args
-    _join = jl
-    return jl
-
-
-# ---- the third companion library: landmark evidence and pruning (include/slamhip_evidence.h) --------------------------------
-# Same arrangement again: libslamhip_evidence.so links against libslamhip.so (run path $ORIGIN), works on its particle-filter
-# handles and is opened when the first evidence object is made, not at import.
-EVIDENCE_LIB_PATH = os.path.join(_HERE, "libslamhip_evidence.so")
+# ---- evidence: landmark evidence and pruning, opened when the first evidence object is made ----------------------------------
 SLAM_PF_EVIDENCE_EMPTY = -128
 SLAM_PF_EVIDENCE_MAXOBS = 64
 _i64p = C.POINTER(C.c_int64)
@@ -262,37 +238,10 @@ EVIDENCE_SIGNATURES = {
     "slam_pf_evidence_get": (C.c_int, [_h, C.c_void_p]),
 }
 
-_evidence = None
+evidence_lib = Companion("evidence", EVIDENCE_SIGNATURES)
+EVIDENCE_LIB_PATH = evidence_lib.path
 
-
-def evidence_lib():
-    """libslamhip_evidence.so, opened on first use.  No fallback: missing or unloadable is an ImportError.  Refuses
-    SLAMHIP_LIBRARY for the reason frame_lib() gives: the handles would belong to another library than the one the companion is
-    linked against."""
-    global _evidence
-    if _evidence is not None:
-        return _evidence
-    if os.path.abspath(LIB_PATH) != os.path.join(_HERE, "libslamhip.so"):
-        raise ImportError(f"libslamhip_evidence.so is linked against {os.path.join(_HERE, 'libslamhip.so')}; the handles of "
-                          f"{LIB_PATH} (SLAMHIP_LIBRARY) cannot be passed to it")
-    if not os.path.exists(EVIDENCE_LIB_PATH):
-        raise ImportError(f"{EVIDENCE_LIB_PATH} is missing: build it with `make -C slam.jl_amd/csrc`.  slam.jl_amd has no CPU fallback.")
-    try:
-        el = C.CDLL(EVIDENCE_LIB_PATH)
-    except OSError as e:  # pragma: no cover - depends on the machine
-        raise ImportError(f"cannot load {EVIDENCE_LIB_PATH}: {e}.  slam.jl_amd has no CPU fallback.") from e
-    for name, (res, args) in EVIDENCE_SIGNATURES.items():
-        fn = getattr(el, name)
-        fn.restype = res
-        fn.argtypes = args
-    _evidence = el
-    return el
-
-
-# ---- the fourth companion library: joint-compatibility data association (include/slamhip_jc.h) -------------------------------
-# Same arrangement again: libslamhip_jc.so links against libslamhip.so (run path $ORIGIN), works on its EKF handles and is
-# opened when the first search workspace is made, not at import.
-JC_LIB_PATH = os.path.join(_HERE, "libslamhip_jc.so")
+# ---- jc: joint-compatibility data association, opened when the first search workspace is made -------------------------------
 SLAM_JC_MAXOBS = 64
 SLAM_JC_MAXCAND = 8
 SLAM_JC_NODE_CAP = 40000
@@ -305,36 +254,10 @@ JC_SIGNATURES = {
     "slam_ekf_joint_nis": (C.c_int, [_h, _dp, _ip, C.c_int, _dp, _dp]),
 }
 
-_jc = None
+jc_lib = Companion("jc", JC_SIGNATURES)
+JC_LIB_PATH = jc_lib.path
 
-
-def jc_lib():
-    """libslamhip_jc.so, opened on first use.  No fallback: missing or unloadable is an ImportError.  Refuses SLAMHIP_LIBRARY
-    for the reason frame_lib() gives: the handles would belong to another library than the one the companion is linked against."""
-    global _jc
-    if _jc is not None:
-        return _jc
-    if os.path.abspath(LIB_PATH) != os.path.join(_HERE, "libslamhip.so"):
-        raise ImportError(f"libslamhip_jc.so is linked against {os.path.join(_HERE, 'libslamhip.so')}; the handles of "
-                          f"{LIB_PATH} (SLAMHIP_LIBRARY) cannot be passed to it")
-    if not os.path.exists(JC_LIB_PATH):
-        raise ImportError(f"{JC_LIB_PATH} is missing: build it with `make -C slam.jl_amd/csrc`.  slam.jl_amd has no CPU fallback.")
-    try:
-        cl = C.CDLL(JC_LIB_PATH)
-    except OSError as e:  # pragma: no cover - depends on the machine
-        raise ImportError(f"cannot load {JC_LIB_PATH}: {e}.  slam.jl_amd has no CPU fallback.") from e
-    for name, (res, args) in JC_SIGNATURES.items():
-        fn = getattr(cl, name)
-        fn.restype = res
-        fn.argtypes = args
-    _jc = cl
-    return cl
-
-
-# ---- the fifth companion library: per-particle trajectory history for FastSLAM (include/slamhip_path.h) ----------------------
-# Same arrangement again: libslamhip_path.so links against libslamhip.so (run path $ORIGIN), works on its particle-filter
-# handles and is opened when the first path object is made, not at import.
-PATH_LIB_PATH = os.path.join(_HERE, "libslamhip_path.so")
+# ---- path: per-particle trajectory history for FastSLAM, opened when the first path object is made --------------------------
 SLAM_PF_PATH_MAXTRACE = 4096
 
 #: every symbol include/slamhip_path.h declares
@@ -351,37 +274,10 @@ PATH_SIGNATURES = {
     "slam_pf_path_survivors": (C.c_int, [_h, _i64p]),
 }
 
-_path = None
+path_lib = Companion("path", PATH_SIGNATURES)
+PATH_LIB_PATH = path_lib.path
 
-
-def path_lib():
-    """libslamhip_path.so, opened on first use.  No fallback: missing or unloadable is an ImportError.  Refuses SLAMHIP_LIBRARY
-    for the reason frame_lib() gives: the handles would belong to another library than the one the companion is linked against."""
-    global _path
-    if _path is not None:
-        return _path
-    if os.path.abspath(LIB_PATH) != os.path.join(_HERE, "libslamhip.so"):
-        raise ImportError(f"libslamhip_path.so is linked against {os.path.join(_HERE, 'libslamhip.so')}; the handles of "
-                          f"{LIB_PATH} (SLAMHIP_LIBRARY) cannot be passed to it")
-    if not os.path.exists(PATH_LIB_PATH):
-        raise ImportError(f"{PATH_LIB_PATH} is missing: build it with `make -C slam.jl_amd/csrc`.  slam.jl_amd has no CPU fallback.")
-    try:
-        pl = C.CDLL(PATH_LIB_PATH)
-    except OSError as e:  # pragma: no cover - depends on the machine
-        raise ImportError(f"cannot load {PATH_LIB_PATH}: {e}.  slam.jl_amd has no CPU fallback.") from e
-    for name, (res, args) in PATH_SIGNATURES.items():
-        fn = getattr(pl, name)
-        fn.restype = res
-        fn.argtypes = args
-    _path = pl
-    return pl
-
-
-# ---- the sixth companion library: an EKF state copied, grown or extracted between two handles (include/slamhip_copy.h) --------
-# Same arrangement again: libslamhip_copy.so links against libslamhip.so (run path $ORIGIN), works on its EKF handles and is
-# opened at the first copy, not at import.
-COPY_LIB_PATH = os.path.join(_HERE, "libslamhip_copy.so")
-
+# ---- copy: an EKF state copied, grown or extracted between two handles, opened at the first copy ----------------------------
 #: every symbol include/slamhip_copy.h declares
 COPY_SIGNATURES = {
     "slam_ekf_capacity": (C.c_int, [_h, C.POINTER(C.c_int)]),
@@ -389,74 +285,20 @@ COPY_SIGNATURES = {
     "slam_ekf_select": (C.c_int, [_h, _h, _ip, C.c_int]),
 }
 
-_copy = None
+copy_lib = Companion("copy", COPY_SIGNATURES)
+COPY_LIB_PATH = copy_lib.path
 
-
-def copy_lib():
-    """libslamhip_copy.so, opened on first use.  No fallback: missing or unloadable is an ImportError.  Refuses SLAMHIP_LIBRARY
-    for the reason frame_lib() gives: the handles would belong to another library than the one the companion is linked against."""
-    global _copy
-    if _copy is not None:
-        return _copy
-    if os.path.abspath(LIB_PATH) != os.path.join(_HERE, "libslamhip.so"):
-        raise ImportError(f"libslamhip_copy.so is linked against {os.path.join(_HERE, 'libslamhip.so')}; the handles of "
-                          f"{LIB_PATH} (SLAMHIP_LIBRARY) cannot be passed to it")
-    if not os.path.exists(COPY_LIB_PATH):
-        raise ImportError(f"{COPY_LIB_PATH} is missing: build it with `make -C slam.jl_amd/csrc`.  slam.jl_amd has no CPU fallback.")
-    try:
-        yl = C.CDLL(COPY_LIB_PATH)
-    except OSError as e:  # pragma: no cover - depends on the machine
-        raise ImportError(f"cannot load {COPY_LIB_PATH}: {e}.  slam.jl_amd has no CPU fallback.") from e
-    for name, (res, args) in COPY_SIGNATURES.items():
-        fn = getattr(yl, name)
-        fn.restype = res
-        fn.argtypes = args
-    _copy = yl
-    return yl
-
-
-# ---- the seventh companion library: a state handed between FastSLAM and the EKF (include/slamhip_handover.h) ------------------
-# Same arrangement again: libslamhip_handover.so links against libslamhip.so (run path $ORIGIN), works on its handles of both
-# kinds and is opened at the first hand-over, not at import.
-HANDOVER_LIB_PATH = os.path.join(_HERE, "libslamhip_handover.so")
-
+# ---- handover: a state handed between FastSLAM and the EKF (handles of both kinds), opened at the first hand-over -----------
 #: every symbol include/slamhip_handover.h declares
 HANDOVER_SIGNATURES = {
     "slam_pf_to_ekf": (C.c_int, [_h, _h, _ip, C.c_int, _dp]),
     "slam_ekf_to_pf": (C.c_int, [_h, _h, _ip, C.c_int]),
 }
 
-_handover = None
+handover_lib = Companion("handover", HANDOVER_SIGNATURES)
+HANDOVER_LIB_PATH = handover_lib.path
 
-
-def handover_lib():
-    """libslamhip_handover.so, opened on first use.  No fallback: missing or unloadable is an ImportError.  Refuses SLAMHIP_LIBRARY
-    for the reason frame_lib() gives: the handles would belong to another library than the one the companion is linked against."""
-    global _handover
-    if _handover is not None:
-        return _handover
-    if os.path.abspath(LIB_PATH) != os.path.join(_HERE, "libslamhip.so"):
-        raise ImportError(f"libslamhip_handover.so is linked against {os.path.join(_HERE, 'libslamhip.so')}; the handles of "
-                          f"{LIB_PATH} (SLAMHIP_LIBRARY) cannot be passed to it")
-    if not os.path.exists(HANDOVER_LIB_PATH):
-        raise ImportError(f"{HANDOVER_LIB_PATH} is missing: build it with `make -C slam.jl_amd/csrc`.  slam.jl_amd has no CPU fallback.")
-    try:
-        hl = C.CDLL(HANDOVER_LIB_PATH)
-    except OSError as e:  # pragma: no cover - depends on the machine
-        raise ImportError(f"cannot load {HANDOVER_LIB_PATH}: {e}.  slam.jl_amd has no CPU fallback.") from e
-    for name, (res, args) in HANDOVER_SIGNATURES.items():
-        fn = getattr(hl, name)
-        fn.restype = res
-        fn.argtypes = args
-    _handover = hl
-    return hl
-
-
-# ---- the eighth companion library: a particle set uploaded, copied, selected and resized (include/slamhip_pfcopy.h) ------------
-# Same arrangement again: libslamhip_pfcopy.so links against libslamhip.so (run path $ORIGIN), works on its particle-filter
-# handles and is opened at the first call, not at import.
-PFCOPY_LIB_PATH = os.path.join(_HERE, "libslamhip_pfcopy.so")
-
+# ---- pfcopy: a particle set uploaded, copied, selected and resized between handles, opened at the first call ----------------
 #: every symbol include/slamhip_pfcopy.h declares
 PFCOPY_SIGNATURES = {
     "slam_pf_get_meta": (C.c_int, [_h, _i64p, C.c_void_p]),
@@ -468,30 +310,11 @@ PFCOPY_SIGNATURES = {
     "slam_pf_pose_bins": (C.c_int, [_h, C.c_double, C.c_double, _i64p]),
 }
 
-_pfcopy = None
+pfcopy_lib = Companion("pfcopy", PFCOPY_SIGNATURES)
+PFCOPY_LIB_PATH = pfcopy_lib.path
 
-
-def pfcopy_lib():
-    """libslamhip_pfcopy.so, opened on first use.  No fallback: missing or unloadable is an ImportError.  Refuses SLAMHIP_LIBRARY
-    for the reason frame_lib() gives: the handles would belong to another library than the one the companion is linked against."""
-    global _pfcopy
-    if _pfcopy is not None:
-        return _pfcopy
-    if os.path.abspath(LIB_PATH) != os.path.join(_HERE, "libslamhip.so"):
-        raise ImportError(f"libslamhip_pfcopy.so is linked against {os.path.join(_HERE, 'libslamhip.so')}; the handles of "
-                          f"{LIB_PATH} (SLAMHIP_LIBRARY) cannot be passed to it")
-    if not os.path.exists(PFCOPY_LIB_PATH):
-        raise ImportError(f"{PFCOPY_LIB_PATH} is missing: build it with `make -C slam.jl_amd/csrc`.  slam.jl_amd has no CPU fallback.")
-    try:
-        kl = C.CDLL(PFCOPY_LIB_PATH)
-    except OSError as e:  # pragma: no cover - depends on the machine
-        raise ImportError(f"cannot load {PFCOPY_LIB_PATH}: {e}.  slam.jl_amd has no CPU fallback.") from e
-    for name, (res, args) in PFCOPY_SIGNATURES.items():
-        fn = getattr(kl, name)
-        fn.restype = res
-        fn.argtypes = args
-    _pfcopy = kl
-    return kl
+#: companion name -> its loader, in the order the libraries were added
+COMPANIONS = {c.name: c for c in (frame_lib, join_lib, evidence_lib, jc_lib, path_lib, copy_lib, handover_lib, pfcopy_lib)}
 
 
 def last_error() -> str:

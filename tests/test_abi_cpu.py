@@ -10,17 +10,15 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests import abi_surface as ABI
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "slamhip.h")
 DIAG_HEADER = os.path.join(ROOT, "include", "slamhip_diag.h")
 
 
 def declared_symbols(headers=(HEADER, DIAG_HEADER)):
-    syms = set()
-    for path in headers:
-        text = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-        syms |= set(re.findall(r"\b(slam_[a-z0-9_]+)\s*\(", text))
-    return sorted(syms)
+    return sorted(set().union(*(ABI.declared(path) for path in headers)))
 
 
 def test_the_boundary_header_stays_small():
@@ -48,8 +46,7 @@ def test_library_exports_every_declared_symbol(pkg):
 def test_product_library_is_not_the_laboratory(pkg):
     """The product library exports exactly what the two headers declare (no slam_exp_* entry, no debug trace) and contains none of
     the experiments build's environment switches: those live in libslamhip_exp.so (make exp), which no test and no bench loads."""
-    out = subprocess.run(["nm", "-D", "--defined-only", pkg._lib.LIB_PATH], capture_output=True, text=True).stdout
-    exported = sorted(line.split()[-1] for line in out.splitlines() if " T " in line and line.split()[-1].startswith("slam_"))
+    exported = sorted(ABI.exported(pkg._lib.LIB_PATH))
     assert exported == declared_symbols(), sorted(set(exported) ^ set(declared_symbols()))
     blob = open(pkg._lib.LIB_PATH, "rb").read()
     for name in (b"SLAMHIP_DEBUG", b"SLAMHIP_FW1", b"SLAMHIP_STAMPS", b"SLAMHIP_WGS", b"SLAMHIP_PB_W", b"SLAMHIP_W1DBG", b"SLAMHIP_SP"):
@@ -188,39 +185,11 @@ def test_telemetry_host_helpers():
     assert json.loads(T.to_json(m)) == {"type": "tracks", "data": {"x": 1}, "timestamp": 3.0}
 
 
-def _julia_ccalls():
-    """(symbol, number of argument types) of every ccall in SLAMHip.jl."""
-    src = open(os.path.join(ROOT, "slam.jl_amd", "SLAMHip.jl")).read()
-    out = []
-    for m in re.finditer(r"ccall\(\(:(slam_[a-z0-9_]+),\s*libslamhip\),\s*([A-Za-z0-9]+),\s*\(", src):
-        i = m.end()                                  # just past the "(" of the argument-type tuple
-        depth, j = 1, i
-        while depth:
-            depth += {"(": 1, ")": -1}.get(src[j], 0)
-            j += 1
-        body = src[i:j - 1]
-        d, parts, cur = 0, [], ""
-        for ch in body:                              # split at top-level commas (Ref{Ptr{Cvoid}} has none, tuples might)
-            if ch in "({":
-                d += 1
-            elif ch in ")}":
-                d -= 1
-            if ch == "," and d == 0:
-                parts.append(cur)
-                cur = ""
-            else:
-                cur += ch
-        if cur.strip():
-            parts.append(cur)
-        out.append((m.group(1), m.group(2), len([x for x in parts if x.strip()])))
-    return out
-
-
 def test_julia_binding_names_exported_symbols_with_the_right_arity(pkg):
     """SLAMHip.jl cannot be executed here (no julia): at least every `ccall((:name, libslamhip), ...)` in it must name a
     symbol the library exports, with as many argument types as the ctypes binding (which the GPU tests exercise) and
     Cint / Cstring as the return type; and the PF surface SURVEY 8b lists must be bound."""
-    calls = _julia_ccalls()
+    calls = ABI.julia_ccalls()
     assert len(calls) >= 28
     sigs = pkg._lib.SIGNATURES
     lib = ctypes.CDLL(pkg._lib.LIB_PATH)

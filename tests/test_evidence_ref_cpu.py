@@ -5,8 +5,6 @@ eight slots for good and a landmark seen later is never stored; with the rule no
 import functools
 import math
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -260,31 +258,11 @@ NAMES = {"slam_pf_evidence_create", "slam_pf_evidence_destroy", "slam_pf_evidenc
 
 
 def test_header_python_and_julia_name_the_same_symbols(pkg):
-    with open(os.path.join(ROOT, "include", "slamhip_evidence.h")) as f:
-        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
-    assert set(re.findall(r"\b(slam_\w+)\s*\(", text)) == NAMES == set(pkg._lib.EVIDENCE_SIGNATURES)
+    """(That the header, the library, this table and the Julia binding name the same symbols: tests/test_companions_cpu.py.)"""
+    assert set(pkg._lib.EVIDENCE_SIGNATURES) == NAMES
     with open(os.path.join(ROOT, "slam.jl_amd", "SLAMHip.jl")) as f:
         src = f.read()
-    for name in NAMES:
-        assert f"(:{name}, libslamhip_evidence)" in src
-    assert "SLAMHIP_EVIDENCE_LIB" in src and "LandmarkEvidence" in src and "step_unknown_pruned!" in src
-    # every ccall into the companion names a bound symbol with the ctypes binding's number of arguments
-    calls = re.findall(r"ccall\(\(:(slam_\w+), libslamhip_evidence\), Cint,\s*\(([^)]*)\)", src)
-    assert {c[0] for c in calls} == NAMES
-    for name, types in calls:
-        nargs = len([t for t in re.sub(r"\{[^}]*\}", "", types).split(",") if t.strip()])
-        assert nargs == len(pkg._lib.EVIDENCE_SIGNATURES[name][1]), name
-    # the companion exports exactly these, the product library none of them, and it finds the product library beside itself
-    nm = lambda path: {line.split()[-1] for line in subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True,
-                                                                   text=True).stdout.splitlines()
-                       if " T " in line and line.split()[-1].startswith("slam_")}
-    assert nm(pkg._lib.EVIDENCE_LIB_PATH) == NAMES
-    assert not (NAMES & nm(pkg._lib.LIB_PATH))
-    needed = subprocess.run(["readelf", "-d", pkg._lib.EVIDENCE_LIB_PATH], capture_output=True, text=True).stdout
-    assert "libslamhip.so" in needed and "$ORIGIN" in needed
-    lib = pkg._lib.evidence_lib()
-    for name in NAMES:
-        assert getattr(lib, name) is not None
+    assert "LandmarkEvidence" in src and "step_unknown_pruned!" in src
     assert callable(pkg.LandmarkEvidence) and callable(pkg.FastSLAM.step_unknown_pruned)
 
 

@@ -8,7 +8,6 @@ import ctypes
 import math
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -24,27 +23,10 @@ R, GATE1, GATE2 = JS.R, JS.GATE1, JS.GATE2
 FIELDS = ("pairings", "tests", "exhausted", "truncated", "candidates", "deepest")
 
 
-def _declared(path):
-    text = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    return set(re.findall(r"\b(slam_[a-z0-9_]+)\s*\(", text))
-
-
-def _exports(path):
-    out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True).stdout
-    return {line.split()[-1] for line in out.splitlines() if " T " in line and line.split()[-1].startswith("slam_")}
-
-
 def test_the_entry_points_are_declared_in_the_jc_header_exported_and_bound(pkg):
+    """(That the header, the library, this table and the Julia binding name the same symbols: tests/test_companions_cpu.py.)"""
     L = pkg._lib
-    assert _declared(os.path.join(ROOT, "include", "slamhip_jc.h")) == NAMES == set(L.JC_SIGNATURES)
-    for other in ("slamhip.h", "slamhip_diag.h", "slamhip_frame.h", "slamhip_join.h", "slamhip_evidence.h"):
-        assert not NAMES & _declared(os.path.join(ROOT, "include", other))
-    assert _exports(L.JC_LIB_PATH) == NAMES
-    for path in (L.LIB_PATH, L.FRAME_LIB_PATH, L.JOIN_LIB_PATH, L.EVIDENCE_LIB_PATH):
-        assert not NAMES & _exports(path)
-    assert not NAMES & set(L.SIGNATURES)
-    needed = subprocess.run(["readelf", "-d", L.JC_LIB_PATH], capture_output=True, text=True).stdout
-    assert "libslamhip.so" in needed and "$ORIGIN" in needed
+    assert set(L.JC_SIGNATURES) == NAMES
     res, args = L.JC_SIGNATURES["slam_ekf_associate_joint"]
     assert res is ctypes.c_int and args[7] is ctypes.c_int64 and len(args) == 10
     header = open(os.path.join(ROOT, "include", "slamhip_jc.h")).read()
@@ -52,9 +34,6 @@ def test_the_entry_points_are_declared_in_the_jc_header_exported_and_bound(pkg):
         assert int(re.search(rf"#define\s+{name}\s+(\d+)", header).group(1)) == val
     assert (L.SLAM_JC_MAXOBS, L.SLAM_JC_MAXCAND) == (JR.MAXOBS, JR.MAXCAND)
     src = open(os.path.join(ROOT, "slam.jl_amd", "SLAMHip.jl")).read()
-    for name in NAMES:
-        assert f"(:{name}, libslamhip_jc)" in src
-    assert "SLAMHIP_JC_LIB" in src
     head = src.split("const libslamhip")[0]
     for name in ("associate_joint", "observe_joint!", "joint_nis", "chi2_table"):
         assert name in head

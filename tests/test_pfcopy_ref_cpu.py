@@ -1,15 +1,13 @@
 """CPU checks of tests/pfcopy_ref.py (the literal model of include/slamhip_pfcopy.h) and of the boundary of the eighth companion
 library: ExactInto against resample_ref.Exact and the device-order model, the undecided cap on the cells the GPU test uses, every
 mutant of the model caught, the KLD count against hand values, the bins against np.unique, the Julia ccalls and the exports."""
-import ctypes
 import math
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
+from tests import abi_surface as ABI
 from tests import pfcopy_ref as PR
 from tests import resample_ref as RR
 
@@ -184,24 +182,10 @@ def test_kld_count_by_hand(pkg):
 
 
 # ---- the boundary of the eighth companion library -----------------------------------------------------------------------------------
-def declared():
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(slam_[a-z0-9_]+)\s*\(", text)))
-
-
 def test_the_library_exports_exactly_what_its_header_declares(pkg):
-    L = pkg._lib
-    assert declared() == sorted(L.PFCOPY_SIGNATURES) and len(declared()) == 7
-    out = subprocess.run(["nm", "-D", "--defined-only", L.PFCOPY_LIB_PATH], capture_output=True, text=True).stdout
-    exported = sorted(line.split()[-1] for line in out.splitlines() if " T " in line and line.split()[-1].startswith("slam_"))
-    assert exported == declared(), sorted(set(exported) ^ set(declared()))
-    lib = ctypes.CDLL(L.PFCOPY_LIB_PATH)
-    assert all(hasattr(lib, s) for s in declared())
-    ldd = subprocess.run(["ldd", L.PFCOPY_LIB_PATH], capture_output=True, text=True).stdout
-    assert "libslamhip.so" in ldd and "torch" not in ldd and "python" not in ldd
-    # the product library itself is unchanged: none of the new names in it
-    main = subprocess.run(["nm", "-D", "--defined-only", L.LIB_PATH], capture_output=True, text=True).stdout
-    assert not [s for s in declared() if re.search(rf"\b{s}\b", main)]
+    """Seven entry points.  (That the header, the library, the ctypes table and the Julia binding name the same symbols, that the
+    library needs neither torch nor python and that the product library has none of the names: tests/test_companions_cpu.py.)"""
+    assert ABI.declared(HEADER) == set(pkg._lib.PFCOPY_SIGNATURES) and len(ABI.declared(HEADER)) == 7
 
 
 def test_bad_arguments_are_status_codes(pkg):
@@ -214,25 +198,8 @@ def test_bad_arguments_are_status_codes(pkg):
 
 
 def test_julia_binding_of_the_new_library(pkg):
+    """(Every ccall's name, return type and number of argument types: tests/test_companions_cpu.py.)"""
     src = open(os.path.join(ROOT, "slam.jl_amd", "SLAMHip.jl")).read()
-    calls = re.findall(r"ccall\(\(:(slam_[a-z0-9_]+),\s*libslamhip_pfcopy\),\s*([A-Za-z0-9]+),\s*\(([^\n]*?)\),\s*\n?", src)
-    sigs = pkg._lib.PFCOPY_SIGNATURES
-    assert len(calls) >= 7
-    for name, ret, args in calls:
-        assert name in sigs and ret == "Cint", (name, ret)
-        depth, nargs, cur = 0, 0, ""
-        for ch in args + ",":
-            if ch in "({":
-                depth += 1
-            elif ch in ")}":
-                depth -= 1
-            if ch == "," and depth == 0:
-                nargs += bool(cur.strip())
-                cur = ""
-            else:
-                cur += ch
-        assert nargs == len(sigs[name][1]), (name, nargs, len(sigs[name][1]))
-    bound = {c[0] for c in calls}
-    assert {"slam_pf_copy", "slam_pf_select", "slam_pf_resize", "slam_pf_upload", "slam_pf_pose_bins", "slam_pf_get_meta"} <= bound
+    assert len(ABI.julia_ccalls("libslamhip_pfcopy")) >= 7
     for word in ("upload!", "resize", "pose_bins", "kld_particle_count", "reserve!(s::PFSlamState", "Base.copy!(dst::PFSlamState", "select(s::PFSlamState"):
         assert word in src, word
