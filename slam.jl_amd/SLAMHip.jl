@@ -18,7 +18,8 @@ export SlamState, EKFSlamState, set_state!, predict, update, add_features, assoc
        PFSlamState, set_pose!, init_landmarks!, pf_predict!, update_known!, step!, step_async!, step_async_batch!, step_unknown!, LandmarkEvidence, evidence_update!, counters, step_unknown_pruned!, flush!,
        PathHistory, record!, path_info, path_record, trace, best_path, mean_path, survivors,
        resample!, mean_pose, weights, particles, pf_map, pf_best_particle, to_ekf, to_particles, peer_blob, attach_peers!, peer_selftest, detach_peers!, comm_info,
-       upload!, resize, pose_bins, kld_particle_count, pf_meta, set_rng!
+       upload!, resize, pose_bins, kld_particle_count, pf_meta, set_rng!,
+       CovFactor, factor, factor!, logdet, isposdef, whiten, nees, sample
 
 const libslamhip = get(ENV, "SLAMHIP_LIB", joinpath(@__DIR__, "libslamhip.so"))
 # the companion library of include/slamhip_frame.h (the rigid frame change); it links against libslamhip.so and lies beside it
@@ -46,6 +47,9 @@ const libslamhip_handover = get(ENV, "SLAMHIP_HANDOVER_LIB", joinpath(@__DIR__, 
 # the companion library of include/slamhip_pfcopy.h (a particle set uploaded, copied, selected and resized between handles), same
 # arrangement (opened at the first copy / select / resize / reserve! / upload! / pose_bins of a particle filter)
 const libslamhip_pfcopy = get(ENV, "SLAMHIP_PFCOPY_LIB", joinpath(@__DIR__, "libslamhip_pfcopy.so"))
+# the extension library of include/ext/slamhip_factor.h (the Cholesky factor of an EKF state's covariance), same arrangement
+# (opened at the first CovFactor)
+const libslamhip_factor = get(ENV, "SLAMHIP_FACTOR_LIB", joinpath(@__DIR__, "libslamhip_factor.so"))
 
 const SLAM_OK = Cint(0)
 const SLAM_PF_HALTED = Cint(1)
@@ -449,6 +453,111 @@ end
 
 "The growth rule of a growing state: twice the capacity, or what is needed if that is more."
 grow_for!(s::EKFSlamState, needed::Integer) = reserve!(s, max(2 * capacity(s), needed))
+
+# ---- the Cholesky factor of cov on the device (include/ext/slamhip_factor.h) ----------------------------------------------------
+"""
+    CovFactor{T}(max_landmarks; device = 0, panel_tiles = 0)
+
+The Cholesky factor L of an EKF state's covariance on the device, L L' = cov, in arithmetic and storage type `T`, with the snapshot
+of x that `factor!` took.  `panel_tiles`: 1, 2 or 4 tile columns per panel, 0 = the default for `T`.
+"""
+mutable struct CovFactor{T<:Union{Float32,Float64}}
+    handle::Ptr{Cvoid}
+    function CovFactor{T}(max_landmarks::Integer; device::Integer = 0, panel_tiles::Integer = 0) where {T}
+        h = Ref{Ptr{Cvoid}}(C_NULL)
+        check(ccall((:slam_ekf_factor_create, libslamhip_factor), Cint, (Ref{Ptr{Cvoid}}, Cint, Cint, Cint, Cint),
+                    h, T === Float32 ? SLAM_F32 : SLAM_F64, max_landmarks, device, panel_tiles))
+        f = new{T}(h[])
+        finalizer(f) do ff
+            ccall((:slam_ekf_factor_destroy, libslamhip_factor), Cint, (Ptr{Cvoid},), ff.handle)
+        end
+        return f
+    end
+end
+
+"    factor!(f, s) -> (status, info): factor `s`'s covariance into `f` (slam_ekf_factor_compute); SLAM_E_NOTPD is returned, not raised."
+function factor!(f::CovFactor, s::EKFSlamState)
+    info = zeros(Float64, 8)
+    rc = ccall((:slam_ekf_factor_compute, libslamhip_factor), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cdouble}), f.handle, handle(s), info)
+    rc == SLAM_OK || rc == SLAM_E_NOTPD || check(rc)
+    rc, info
+end
+
+"    factor(s; T = eltype of s, panel_tiles = 0) -> CovFactor: cov = L L' on the device; an error when a pivot fails.  Synchronises."
+function factor(s::EKFSlamState{S}; T::Type = S, panel_tiles::Integer = 0) where {S}
+    f = CovFactor{T}(capacity(s); device = getfield(s, :device), panel_tiles = panel_tiles)
+    rc, _ = factor!(f, s)
+    check(rc)
+    f
+end
+
+"[n, status, first failing index (0-based) or -1, failing pivot, min l_ii, max l_ii, log det, panel_tiles] of the last factor!."
+function factor_info(f::CovFactor)
+    info = zeros(Float64, 8)
+    check(ccall((:slam_ekf_factor_info, libslamhip_factor), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), f.handle, info))
+    info
+end
+Base.length(f::CovFactor) = Int(factor_info(f)[1])
+
+"log det cov = 2 sum log l_ii (map entropy up to a constant)."
+logdet(f::CovFactor) = factor_info(f)[7]
+
+"""
+    isposdef(s; T = Float64) -> (ok, index, landmark)
+
+Whether cov has a Cholesky factor in `T` arithmetic; if not, the first failing state index (1-based) and its landmark (0: the vehicle).
+"""
+function isposdef(s::EKFSlamState; T::Type = Float64)
+    f = CovFactor{T}(capacity(s); device = getfield(s, :device))
+    rc, info = factor!(f, s)
+    finalize(f)
+    rc == SLAM_OK && return (true, 0, 0)
+    i = Int(info[3])
+    (false, i + 1, i < 3 ? 0 : (i - 3) ÷ 2 + 1)
+end
+
+"    L(f, r0, c0, nr, nc): the block L[r0 : r0 + nr - 1, c0 : c0 + nc - 1] (1-based), zeros above the diagonal."
+function factor_block(f::CovFactor{T}, r0::Integer, c0::Integer, nr::Integer, nc::Integer) where {T}
+    out = Matrix{T}(undef, nr, nc)
+    check(ccall((:slam_ekf_factor_get, libslamhip_factor), Cint, (Ptr{Cvoid}, Cint, Cint, Cint, Cint, Ptr{Cvoid}, Cint),
+                f.handle, r0 - 1, c0 - 1, nr, nc, out, max(nr, 1)))
+    out
+end
+
+"x as the last factor! found it, as Float64."
+function factor_mean(f::CovFactor)
+    x = zeros(Float64, length(f))
+    check(ccall((:slam_ekf_factor_mean, libslamhip_factor), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), f.handle, x))
+    x
+end
+
+"    whiten(f, E) -> (Y, d2): Y = L^-1 E for an n x r matrix of error vectors, r <= 64, and the squared norms of Y's columns (fp64)."
+function whiten(f::CovFactor, E::AbstractMatrix)
+    B = Matrix{Float64}(E)
+    n, r = size(B)
+    Y = similar(B)
+    d2 = zeros(Float64, r)
+    check(ccall((:slam_ekf_factor_solve, libslamhip_factor), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}),
+                f.handle, B, r, n, Y, d2))
+    Y, d2
+end
+
+"    nees(f, x_true): e' cov^-1 e with e = mean - x_true, the heading difference wrapped by mpi_to_pi."
+function nees(f::CovFactor, x_true::AbstractVector)
+    e = factor_mean(f) .- x_true
+    e[3] = mpi_to_pi(e[3])
+    whiten(f, reshape(e, :, 1))[2][1]
+end
+
+"    sample(f, Z): mean .+ L Z for an n x r matrix Z of the caller's standard normals, r <= 64: joint samples of the state."
+function sample(f::CovFactor, Z::AbstractMatrix)
+    Zd = Matrix{Float64}(Z)
+    n, r = size(Zd)
+    out = similar(Zd)
+    check(ccall((:slam_ekf_factor_multiply, libslamhip_factor), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}),
+                f.handle, Zd, r, n, out))
+    factor_mean(f) .+ out
+end
 
 "feature_ellipses(x, cov) of the browser monitor (sim/browser/wsserver.jl:72-85): 5 x N [cx; cy; rx; ry; phi], on the device."
 function feature_ellipses(s::EKFSlamState)

@@ -316,6 +316,28 @@ PFCOPY_LIB_PATH = pfcopy_lib.path
 #: companion name -> its loader, in the order the libraries were added
 COMPANIONS = {c.name: c for c in (frame_lib, join_lib, evidence_lib, jc_lib, path_lib, copy_lib, handover_lib, pfcopy_lib)}
 
+# ---- the extensions: libraries wired like a companion whose header lives in include/ext/ ------------------------------------
+# ---- factor: the Cholesky factor of an EKF state's covariance, opened when the first factor object is made --------------------
+SLAM_FACTOR_MAXRHS = 64
+
+#: every symbol include/ext/slamhip_factor.h declares
+FACTOR_SIGNATURES = {
+    "slam_ekf_factor_create": (C.c_int, [C.POINTER(_h), C.c_int, C.c_int, C.c_int, C.c_int]),
+    "slam_ekf_factor_destroy": (C.c_int, [_h]),
+    "slam_ekf_factor_compute": (C.c_int, [_h, _h, _dp]),
+    "slam_ekf_factor_info": (C.c_int, [_h, _dp]),
+    "slam_ekf_factor_get": (C.c_int, [_h, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]),
+    "slam_ekf_factor_mean": (C.c_int, [_h, _dp]),
+    "slam_ekf_factor_solve": (C.c_int, [_h, _dp, C.c_int, C.c_int, _dp, _dp]),
+    "slam_ekf_factor_multiply": (C.c_int, [_h, _dp, C.c_int, C.c_int, _dp]),
+}
+
+factor_lib = Companion("factor", FACTOR_SIGNATURES)
+FACTOR_LIB_PATH = factor_lib.path
+
+#: extension name -> its loader
+EXTENSIONS = {"factor": factor_lib}
+
 
 def last_error() -> str:
     msg = lib.slam_last_error()

@@ -37,6 +37,7 @@ __all__ = [
     "find_duplicates", "merge_features", "merge_features_", "merge_in_batches",
     "chi2_table", "associate_joint", "observe_joint",
     "copy_state", "select_features", "select_map", "grown_capacity",
+    "CovarianceFactor",
 ]
 
 _DTYPES = {"f32": (SLAM_F32, np.float32), "f64": (SLAM_F64, np.float64),
@@ -380,6 +381,55 @@ class EKFSlamState(SlamState):
             new.close()
             raise
         return new
+
+    # -- the Cholesky factor of cov on the device (include/ext/slamhip_factor.h) ---------------------
+    def factor(self, dtype=None, out=None, panel_tiles=0):
+        """cov = L L' on the device (slam_ekf_factor_compute): a :class:`CovarianceFactor`.  ``dtype``: the arithmetic and storage
+        type of L, default this state's; "f64" over an fp32 state is the trustworthy check of it (an fp32 factor of an fp64 state is
+        refused).  ``out``: an existing factor to compute into (its dtype, capacity and panel width are kept).  ``panel_tiles``:
+        1, 2 or 4 tile columns per panel, 0 = the default for the dtype.  NotPositiveDefinite when a pivot fails (the factor
+        passed as ``out`` then holds the failing index in ``.info``).  This state is only read.  Synchronises."""
+        if out is None:
+            new = CovarianceFactor(self.np_dtype if dtype is None else dtype, self.capacity, device=self.device,
+                                   panel_tiles=panel_tiles)
+            try:
+                new.compute(self)
+            except Exception:
+                new.close()
+                raise
+            return new
+        out.compute(self)
+        return out
+
+    def is_positive_definite(self, dtype="f64"):
+        """``(ok, index, landmark)``: whether cov has a Cholesky factor in ``dtype`` arithmetic; if not, the first failing state
+        index (0-based) and the landmark it belongs to (1-based; 0: the vehicle), else (True, -1, -1).  A failing pivot raises
+        nothing."""
+        f = CovarianceFactor(dtype, self.capacity, device=self.device)
+        try:
+            try:
+                f.compute(self)
+            except _lib.NotPositiveDefinite:
+                i = int(f.info[2])
+                return False, i, (0 if i < 3 else (i - 3) // 2 + 1)
+            return True, -1, -1
+        finally:
+            f.close()
+
+    def nees(self, x_true, ids=None):
+        """The normalised estimation error squared e' cov^-1 e against the true state ``x_true`` (3 + 2 N values, or 3 + 2 len(ids)
+        with ``ids``), e = x - x_true with the heading wrapped: over the whole map, or over the vehicle and the landmarks ``ids``
+        (1-based) through select() -- the marginal -- and its factor.  In fp64 arithmetic whatever the state's dtype."""
+        sub = self.select(ids) if ids is not None else None
+        try:
+            f = (sub if sub is not None else self).factor(dtype="f64")
+            try:
+                return f.nees(x_true)
+            finally:
+                f.close()
+        finally:
+            if sub is not None:
+                sub.close()
 
     # -- hand-over to the particle filter (include/slamhip_handover.h) -------------------------------
     def to_particles(self, n, seed=0, ids=None, max_landmarks=None, neff_frac=0.75):
@@ -859,6 +909,116 @@ class EKFSlamState(SlamState):
 
 
 # ---- the reference's function surface ---------------------------------------------------
+
+class CovarianceFactor:
+    """The Cholesky factor L of an EKF state's covariance, on the device (include/ext/slamhip_factor.h): L L' = cov, in the
+    state's own tile-major layout, with the snapshot of x that ``compute`` took.  ``dtype`` is the arithmetic and storage type of
+    L; ``max_landmarks`` the capacity; ``panel_tiles`` 1, 2, 4 or 0 (the default for the dtype)."""
+
+    def __init__(self, dtype="f64", max_landmarks=64, device=0, panel_tiles=0):
+        code, npdt = _DTYPES[dtype]
+        self.np_dtype = npdt
+        self.max_landmarks = int(max_landmarks)
+        self.device = int(device)
+        self._h = C.c_void_p()
+        self._flib = _lib.factor_lib()
+        check(self._flib.slam_ekf_factor_create(C.byref(self._h), code, self.max_landmarks, self.device, int(panel_tiles)))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            self._flib.slam_ekf_factor_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def compute(self, state):
+        """Factor ``state``'s covariance into this object; NotPositiveDefinite when a pivot fails (``info`` then names it and
+        every read-out is refused until a compute succeeds).  Synchronises."""
+        if not isinstance(state, EKFSlamState):
+            raise TypeError("compute needs an EKFSlamState")
+        info = np.zeros(8)
+        check(self._flib.slam_ekf_factor_compute(self._h, state._h, _ptr(info)))
+        return info
+
+    @property
+    def info(self):
+        """[n, status, first failing index or -1, failing pivot, min l_ii, max l_ii, log det, panel_tiles] of the last compute."""
+        info = np.zeros(8)
+        check(self._flib.slam_ekf_factor_info(self._h, _ptr(info)))
+        return info
+
+    n = property(lambda self: int(self.info[0]))
+    min_pivot = property(lambda self: float(self.info[4]), doc="the smallest l_ii")
+    max_pivot = property(lambda self: float(self.info[5]), doc="the largest l_ii")
+    logdet = property(lambda self: float(self.info[6]), doc="log det cov = 2 sum log l_ii")
+    panel_tiles = property(lambda self: int(self.info[7]))
+
+    def L(self, r0=0, c0=0, nr=None, nc=None):
+        """L[r0 : r0 + nr, c0 : c0 + nc] (0-based; default: to the end), zeros above the diagonal, in the factor's dtype."""
+        n = self.n
+        nr = n - int(r0) if nr is None else int(nr)
+        nc = n - int(c0) if nc is None else int(nc)
+        out = np.empty((nr, nc), dtype=self.np_dtype, order="F")
+        check(self._flib.slam_ekf_factor_get(self._h, int(r0), int(c0), nr, nc, out.ctypes.data, max(nr, 1)))
+        return out
+
+    def mean(self):
+        """x as ``compute`` found it, as float64."""
+        out = np.empty(max(self.n, 1))
+        check(self._flib.slam_ekf_factor_mean(self._h, _ptr(out)))
+        return out[:self.n]
+
+    def _rhs(self, A):
+        A = np.asarray(A, dtype=np.float64)
+        vec = A.ndim == 1
+        A = np.asfortranarray(A.reshape(-1, 1) if vec else A)
+        if A.ndim != 2 or A.shape[0] != self.n:
+            raise ValueError(f"expected {self.n} rows")
+        return A, vec
+
+    def whiten(self, E, return_d2=False):
+        """``L^-1 E`` for an n-vector or an n x r matrix of error vectors (any r: in slices of 64 columns), fp64 arithmetic; with
+        ``return_d2`` also the squared norms of the result's columns."""
+        E, vec = self._rhs(E)
+        n, r = E.shape
+        Y = np.empty((n, r), order="F")
+        d2 = np.empty(r)
+        for c in range(0, r, _lib.SLAM_FACTOR_MAXRHS):
+            w = min(_lib.SLAM_FACTOR_MAXRHS, r - c)
+            Bc, Yc, dc = np.asfortranarray(E[:, c:c + w]), np.empty((n, w), order="F"), np.empty(w)
+            check(self._flib.slam_ekf_factor_solve(self._h, _ptr(Bc), w, n, _ptr(Yc), _ptr(dc)))
+            Y[:, c:c + w], d2[c:c + w] = Yc, dc
+        Y = Y[:, 0] if vec else Y
+        return (Y, (float(d2[0]) if vec else d2)) if return_d2 else Y
+
+    def colour(self, Z):
+        """``L Z`` for an n-vector or an n x r matrix (any r: in slices of 64 columns), fp64 arithmetic."""
+        Z, vec = self._rhs(Z)
+        n, r = Z.shape
+        out = np.empty((n, r), order="F")
+        for c in range(0, r, _lib.SLAM_FACTOR_MAXRHS):
+            w = min(_lib.SLAM_FACTOR_MAXRHS, r - c)
+            Zc, Oc = np.asfortranarray(Z[:, c:c + w]), np.empty((n, w), order="F")
+            check(self._flib.slam_ekf_factor_multiply(self._h, _ptr(Zc), w, n, _ptr(Oc)))
+            out[:, c:c + w] = Oc
+        return out[:, 0] if vec else out
+
+    def nees(self, x_true):
+        """e' cov^-1 e with e = mean - x_true, the heading difference wrapped by mpi_to_pi."""
+        e = self.mean() - _dbl(x_true, self.n)
+        e[2] = mpi_to_pi(e[2])
+        return self.whiten(e, return_d2=True)[1]
+
+    def sample(self, count, rng):
+        """``count`` joint samples of the state as the columns of an n x count array: mean + L Z with Z = rng.standard_normal((n,
+        count)) from the caller's ``numpy.random.Generator``, so the draw is the caller's to reproduce."""
+        Z = rng.standard_normal((self.n, int(count)))
+        return self.mean()[:, None] + self.colour(Z)
+
 
 def _state_of(ref_or_state):
     if isinstance(ref_or_state, EKFSlamState):

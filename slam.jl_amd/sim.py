@@ -143,6 +143,9 @@ class SimLog:
     joined: list = field(default_factory=list)          # (observation step, first_new, landmarks joined, landmarks after) per join (sim(submap_steps=k))
     true_track: list = field(default_factory=list)
     slam_track: list = field(default_factory=list)
+    nees: list = field(default_factory=list)            # (predict-step index, NEES, degrees of freedom 3 + 2 N) per sim(nees_every=k) sample
+    nees_truth: list = field(default_factory=list)      # the true state each sample was held against (pose, then the map's landmarks)
+    landmark_tags: object = None                        # sim(nees_every=k): 1-based true landmark behind each map landmark at the end
     best_path: object = None                            # [L, 3]: the best particle's path at the end of the run (a PFSlamState after track_path)
 
 
@@ -166,7 +169,7 @@ def default_QR():
 
 def sim(filt, waypoints: np.ndarray, landmarks: np.ndarray, seed: int, nlaps: int = 2,
         max_steps: int = 100000, monitor=None, fused: bool = False, prune_after=None, merge_gate=None,
-        submap_steps=None, association: str = "nearest") -> SimLog:
+        submap_steps=None, association: str = "nearest", nees_every=None) -> SimLog:
     """The loop of sim/ekfslam-sim.jl:80-141 without sleep/pause.
 
     ``filt`` must already hold the initial state (x = initial pose, P = 0).
@@ -190,12 +193,21 @@ def sim(filt, waypoints: np.ndarray, landmarks: np.ndarray, seed: int, nlaps: in
     ``association``: "nearest" (default) is the reference's nearest neighbour.  "joint" (no counterpart in the reference) takes
     the decisions from the joint-compatibility search, ``filt.associate_joint`` / ``filt.observe_joint`` with their defaults: no
     landmark is used twice in one step (at most 64 observations per step; not available with ``submap_steps``).
+    ``nees_every``: None (default) changes nothing.  An integer k (no counterpart in the reference): after every k-th step the
+    consistency measure ``filt.nees(x_true)`` -- e' P^-1 e over the vehicle and every landmark seen so far, from the factor of P
+    on the device -- is recorded in ``log.nees`` with its degrees of freedom, and ``x_true`` in ``log.nees_truth``.  ``x_true`` is the
+    simulator's vehicle pose and, for each landmark of the map, the TRUE correspondence: the simulator's landmark whose observation
+    created it (the sensor's tags, which the filter never sees, are carried here through every new feature, removal and merge; a
+    merged landmark keeps the tag of its lowest old id).  A wrong association therefore counts against the filter, as it should.
+    A matrix that has no Cholesky factor is recorded as NaN.  Not available with ``submap_steps`` (the truth is in another frame there).
     """
     if association not in ("nearest", "joint"):
         raise ValueError('association must be "nearest" or "joint"')
     joint = association == "joint"
     if joint and submap_steps is not None:
         raise ValueError('association="joint" is not available with submap_steps')
+    if nees_every is not None and (submap_steps is not None or int(nees_every) < 1):
+        raise ValueError("nees_every must be a positive step count and is not available with submap_steps")
     if submap_steps is not None:
         if prune_after is not None:
             raise ValueError("prune_after counts matches in one map: not available with submap_steps")
@@ -208,6 +220,7 @@ def sim(filt, waypoints: np.ndarray, landmarks: np.ndarray, seed: int, nlaps: in
     nsteps = 0
     born = np.zeros(0, dtype=np.int64)      # prune_after: observation step that created landmark j (at [j - 1]) ...
     hits = np.zeros(0, dtype=np.int64)      # ... and its matches since
+    tags = np.zeros(0, dtype=np.int64)      # nees_every: the true landmark (1-based) whose observation created landmark j
     while vehicle.waypoint_id != 0 and nsteps < max_steps:
         steer(vehicle, waypoints, D_MIN, DT)                              # :85
         if vehicle.waypoint_id == 0 and nlaps > 1:                        # :88-91
@@ -221,7 +234,7 @@ def sim(filt, waypoints: np.ndarray, landmarks: np.ndarray, seed: int, nlaps: in
         dtsum += DT                                                       # :102
         if dtsum > DT_OBS:                                                # :105 (fires every 9th step)
             dtsum = 0.0
-            z, _tags = get_observations(vehicle, landmarks, R, rng)       # :108
+            z, ztags = get_observations(vehicle, landmarks, R, rng)       # :108
             if fused:
                 assoc = np.asarray(filt.observe_joint(z, R, GATE1, GATE2)[0] if joint else filt.observe(z, R, GATE1, GATE2))   # :114-120 in one call
                 idf = assoc[assoc > 0]
@@ -233,6 +246,8 @@ def sim(filt, waypoints: np.ndarray, landmarks: np.ndarray, seed: int, nlaps: in
             log.obs_steps.append(nsteps)
             log.observations.append(np.array(z))
             log.assoc.append((np.asarray(idf).reshape(-1).tolist(), int(np.asarray(zn).reshape(2, -1).shape[1])))
+            if nees_every is not None:
+                tags = np.concatenate([tags, ztags[_columns_of(z, zn)]])
             if prune_after is not None:
                 t = len(log.obs_steps) - 1
                 np.add.at(hits, np.asarray(idf, dtype=np.int64).reshape(-1) - 1, 1)
@@ -245,11 +260,18 @@ def sim(filt, waypoints: np.ndarray, landmarks: np.ndarray, seed: int, nlaps: in
                     log.pruned.append((t, (stale + 1).tolist()))
                     left = new_index > 0
                     born, hits = born[left], hits[left]
+                    if nees_every is not None:
+                        tags = tags[left]
             if merge_gate is not None:
                 pairs, _count = filt.find_duplicates(merge_gate)
                 if len(pairs):
                     new_index = np.asarray(filt.merge_landmarks(pairs), dtype=np.int64)
                     log.merged.append((len(log.obs_steps) - 1, np.asarray(pairs).tolist()))
+                    if nees_every is not None:
+                        stays = np.flatnonzero(new_index > 0)[::-1]       # (the lowest old id of a merged group is written last)
+                        ntags = np.zeros(int(new_index.max()) if new_index.size else 0, dtype=np.int64)
+                        ntags[new_index[stays] - 1] = tags[stays]
+                        tags = ntags
                     if prune_after is not None:
                         nleft = int(new_index.max()) if new_index.size else 0
                         nborn = np.full(nleft, np.iinfo(np.int64).max, dtype=np.int64)
@@ -260,11 +282,45 @@ def sim(filt, waypoints: np.ndarray, landmarks: np.ndarray, seed: int, nlaps: in
         nsteps += 1
         log.true_track.append(np.array(vehicle.pose))
         log.slam_track.append(np.array(filt.pose()))
+        if nees_every is not None and nsteps % int(nees_every) == 0:
+            value, x_true = _nees_against_truth(filt, vehicle, landmarks, tags)
+            log.nees.append((nsteps, value, int(x_true.size)))
+            log.nees_truth.append(x_true)
         if monitor is not None:
             monitor(vehicle, filt, nsteps)
+    if nees_every is not None:
+        log.landmark_tags = tags
     if getattr(filt, "path_history", None) is not None:                   # a PFSlamState that tracks its path (FastSLAM.track_path)
         log.best_path = np.array(filt.path())
     return log
+
+
+def _columns_of(z, zn):
+    """The columns of z (2 x nz) that zn (2 x nn) was taken from, in zn's order: the filter hands new-feature observations back as
+    they came, so they are found by value."""
+    z = np.asarray(z, dtype=float).reshape(2, -1)
+    zn = np.asarray(zn, dtype=float).reshape(2, -1)
+    cols = np.zeros(zn.shape[1], dtype=np.int64)
+    for k in range(zn.shape[1]):
+        hit = np.flatnonzero((z[0] == zn[0, k]) & (z[1] == zn[1, k]))
+        if hit.size != 1:
+            raise RuntimeError("a new-feature observation is not one of the step's observations")
+        cols[k] = hit[0]
+    return cols
+
+
+def _nees_against_truth(filt, vehicle, landmarks, tags):
+    """(NEES, x_true) of ``filt`` against the simulator's truth: the vehicle pose and, per map landmark, the true landmark
+    ``tags`` names (1-based).  NaN for a matrix without a Cholesky factor."""
+    from ._lib import NotPositiveDefinite
+    truth = np.asarray(landmarks, dtype=float).reshape(2, -1)
+    if 3 + 2 * tags.size != filt.n:
+        raise RuntimeError("the tags do not follow the map")
+    x_true = np.concatenate([np.asarray(vehicle.pose, dtype=float), truth[:, tags - 1].T.reshape(-1)])
+    try:
+        return float(filt.nees(x_true)), x_true
+    except NotPositiveDefinite:
+        return float("nan"), x_true
 
 
 def _compose(base, local):
