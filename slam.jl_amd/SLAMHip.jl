@@ -19,7 +19,8 @@ export SlamState, EKFSlamState, set_state!, predict, update, add_features, assoc
        PathHistory, record!, path_info, path_record, trace, best_path, mean_path, survivors,
        resample!, mean_pose, weights, particles, pf_map, pf_best_particle, to_ekf, to_particles, peer_blob, attach_peers!, peer_selftest, detach_peers!, comm_info,
        upload!, resize, pose_bins, kld_particle_count, pf_meta, set_rng!,
-       CovFactor, factor, factor!, logdet, isposdef, whiten, nees, sample
+       CovFactor, factor, factor!, logdet, isposdef, whiten, nees, sample,
+       update_linear!, linear_nis, predict_linear!, predict_odometry!, fix_position!, fix_heading!, fix_landmark!
 
 const libslamhip = get(ENV, "SLAMHIP_LIB", joinpath(@__DIR__, "libslamhip.so"))
 # the companion library of include/slamhip_frame.h (the rigid frame change); it links against libslamhip.so and lies beside it
@@ -50,6 +51,9 @@ const libslamhip_pfcopy = get(ENV, "SLAMHIP_PFCOPY_LIB", joinpath(@__DIR__, "lib
 # the extension library of include/ext/slamhip_factor.h (the Cholesky factor of an EKF state's covariance), same arrangement
 # (opened at the first CovFactor)
 const libslamhip_factor = get(ENV, "SLAMHIP_FACTOR_LIB", joinpath(@__DIR__, "libslamhip_factor.so"))
+# the extension library of include/ext/slamhip_linear.h (caller-supplied motion and measurement models for the EKF), same
+# arrangement (opened at the first update_linear! / linear_nis / predict_linear! / predict_odometry!)
+const libslamhip_linear = get(ENV, "SLAMHIP_LINEAR_LIB", joinpath(@__DIR__, "libslamhip_linear.so"))
 
 const SLAM_OK = Cint(0)
 const SLAM_PF_HALTED = Cint(1)
@@ -558,6 +562,84 @@ function sample(f::CovFactor, Z::AbstractMatrix)
                 f.handle, Zd, r, n, out))
     factor_mean(f) .+ out
 end
+
+# ---- caller-supplied models (include/ext/slamhip_linear.h) ------------------------------------------------------------------------
+# H: a k x n matrix (k <= 16 rows of at most 8 non-zeros).  The C interface counts state indices from 0; the Julia matrix's
+# column c is state index c - 1.
+function linear_rows(H::AbstractMatrix)
+    ptr = Cint[0]; idx = Cint[]; val = Float64[]
+    for i in 1:size(H, 1)
+        for c in 1:size(H, 2)
+            H[i, c] == 0 && continue
+            push!(idx, c - 1); push!(val, H[i, c])
+        end
+        push!(ptr, length(idx))
+    end
+    ptr, idx, val
+end
+
+function linear_mask(wrap, innovation::Bool)
+    mask = UInt32(0)
+    for i in wrap
+        mask |= UInt32(1) << (i - 1)                                     # rows are counted from 1 here
+    end
+    mask, Cint(innovation ? 1 : 0)
+end
+
+"""
+    update_linear!(s, H, z, R; wrap = (), innovation = false) -> [v' inv(S) v, log det S, smallest pivot, -1]
+
+The Kalman update from a linear measurement z = H x + noise(R), in place on the device (slam_ekf_update_linear).  `wrap`: the
+rows (1-based) whose innovation is an angle.  `innovation = true`: `z` already is the innovation.
+"""
+function update_linear!(s::EKFSlamState, H::AbstractMatrix, z::AbstractVector, R::AbstractMatrix; wrap = (), innovation::Bool = false)
+    ptr, idx, val = linear_rows(H)
+    mask, mode = linear_mask(wrap, innovation)
+    out = zeros(Float64, 4)
+    check(ccall((:slam_ekf_update_linear, libslamhip_linear), Cint,
+                (Ptr{Cvoid}, Cint, Ptr{Cint}, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, UInt32, Ptr{Cdouble}),
+                handle(s), size(H, 1), ptr, idx, val, Vector{Float64}(z), Matrix{Float64}(R), mode, mask, out))
+    out
+end
+
+"    linear_nis(s, H, z, R; wrap, innovation): what update_linear! would return; the state is only read (the chi-square gate)."
+function linear_nis(s::EKFSlamState, H::AbstractMatrix, z::AbstractVector, R::AbstractMatrix; wrap = (), innovation::Bool = false)
+    ptr, idx, val = linear_rows(H)
+    mask, mode = linear_mask(wrap, innovation)
+    out = zeros(Float64, 4)
+    check(ccall((:slam_ekf_linear_nis, libslamhip_linear), Cint,
+                (Ptr{Cvoid}, Cint, Ptr{Cint}, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, UInt32, Ptr{Cdouble}),
+                handle(s), size(H, 1), ptr, idx, val, Vector{Float64}(z), Matrix{Float64}(R), mode, mask, out))
+    out
+end
+
+"    predict_linear!(s, xv, Gv, Qv): x[1:3] = xv, P_vv = Gv P_vv Gv' + Qv, P_vm = Gv P_vm (slam_ekf_predict_linear)."
+function predict_linear!(s::EKFSlamState, xv::AbstractVector, Gv::AbstractMatrix, Qv::AbstractMatrix)
+    check(ccall((:slam_ekf_predict_linear, libslamhip_linear), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                handle(s), Vector{Float64}(xv), Matrix{Float64}(Gv), Matrix{Float64}(Qv)))
+    nothing
+end
+
+"    predict_odometry!(s, d, Q3): compose the pose with the vehicle-frame increment d = (dx, dy, dtheta) of covariance Q3, on the device."
+function predict_odometry!(s::EKFSlamState, d::AbstractVector, Q3::AbstractMatrix)
+    check(ccall((:slam_ekf_predict_odometry, libslamhip_linear), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}),
+                handle(s), Vector{Float64}(d), Matrix{Float64}(Q3)))
+    nothing
+end
+
+function unit_rows(n::Integer, cols)
+    H = zeros(Float64, length(cols), n)
+    for (i, c) in enumerate(cols)
+        H[i, c] = 1.0
+    end
+    H
+end
+"    fix_position!(s, xy, R): the vehicle is at xy with covariance R (a GPS receiver)."
+fix_position!(s::EKFSlamState, xy, R) = update_linear!(s, unit_rows(length(s), (1, 2)), xy, R)
+"    fix_heading!(s, phi, var): the heading is phi with variance var (a compass); the innovation is wrapped."
+fix_heading!(s::EKFSlamState, phi, var) = update_linear!(s, unit_rows(length(s), (3,)), [phi], fill(Float64(var), 1, 1); wrap = (1,))
+"    fix_landmark!(s, j, xy, R): landmark j was surveyed at xy with covariance R."
+fix_landmark!(s::EKFSlamState, j::Integer, xy, R) = update_linear!(s, unit_rows(length(s), (2 + 2j, 3 + 2j)), xy, R)
 
 "feature_ellipses(x, cov) of the browser monitor (sim/browser/wsserver.jl:72-85): 5 x N [cx; cy; rx; ry; phi], on the device."
 function feature_ellipses(s::EKFSlamState)

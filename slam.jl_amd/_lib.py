@@ -338,6 +338,25 @@ FACTOR_LIB_PATH = factor_lib.path
 #: extension name -> its loader
 EXTENSIONS = {"factor": factor_lib}
 
+# ---- linear: caller-supplied motion and measurement models for the EKF, opened at the first such call --------------------------
+# Wired like factor (the same Makefile rule, the same loader class, the header in include/ext/), but entered in NEITHER table:
+# tests/test_companions_cpu.py and tests/test_factor_ref_cpu.py pin COMPANIONS and EXTENSIONS as they stand, and the surface
+# checks those tables drive are made for this library by tests/test_linear_ref_cpu.py.
+SLAM_LINEAR_MAXROWS = 16
+SLAM_LINEAR_MAXNNZ = 8
+SLAM_LINEAR_MEASURED, SLAM_LINEAR_INNOVATION = 0, 1
+
+#: every symbol include/ext/slamhip_linear.h declares
+LINEAR_SIGNATURES = {
+    "slam_ekf_update_linear": (C.c_int, [_h, C.c_int, _ip, _ip, _dp, _dp, _dp, C.c_int, C.c_uint32, _dp]),
+    "slam_ekf_linear_nis": (C.c_int, [_h, C.c_int, _ip, _ip, _dp, _dp, _dp, C.c_int, C.c_uint32, _dp]),
+    "slam_ekf_predict_linear": (C.c_int, [_h, _dp, _dp, _dp]),
+    "slam_ekf_predict_odometry": (C.c_int, [_h, _dp, _dp]),
+}
+
+linear_lib = Companion("linear", LINEAR_SIGNATURES)
+LINEAR_LIB_PATH = linear_lib.path
+
 
 def last_error() -> str:
     msg = lib.slam_last_error()

@@ -37,7 +37,7 @@ __all__ = [
     "find_duplicates", "merge_features", "merge_features_", "merge_in_batches",
     "chi2_table", "associate_joint", "observe_joint",
     "copy_state", "select_features", "select_map", "grown_capacity",
-    "CovarianceFactor",
+    "CovarianceFactor", "linear_rows",
 ]
 
 _DTYPES = {"f32": (SLAM_F32, np.float32), "f64": (SLAM_F64, np.float64),
@@ -62,6 +62,36 @@ def _small(M):
 
 def _ptr(a, ctype=C.c_double):
     return a.ctypes.data_as(C.POINTER(ctype))
+
+
+def _mat3(M):
+    """3 x 3 matrix -> column-major double[9]."""
+    M = np.asarray(M, dtype=np.float64)
+    if M.shape != (3, 3):
+        raise ValueError("expected a 3 x 3 matrix")
+    return np.ascontiguousarray(M.T).reshape(9)
+
+
+def linear_rows(H, n):
+    """The CSR arrays ``(ptr int32 [k + 1], idx int32, val float64)`` of a linear measurement over n states, as
+    slam_ekf_update_linear takes them.  ``H``: a dense (k, n) array (its non-zeros, in column order) or a list of
+    ``{state index: value}`` rows (in the dict's order).  The library checks the row and index limits."""
+    rows = []
+    if isinstance(H, np.ndarray) or (len(H) and not isinstance(H[0], dict)):
+        D = np.atleast_2d(np.asarray(H, dtype=np.float64))
+        if D.shape[1] != n:
+            raise ValueError(f"H has {D.shape[1]} columns, the state has {n} entries")
+        for r in D:
+            nz = np.flatnonzero(r)
+            rows.append((nz, r[nz]))
+    else:
+        for r in H:
+            rows.append((np.fromiter(r.keys(), dtype=np.int64, count=len(r)), np.fromiter(r.values(), dtype=np.float64, count=len(r))))
+    ptr = np.zeros(len(rows) + 1, dtype=np.int32)
+    ptr[1:] = np.cumsum([len(i) for i, _ in rows])
+    idx = np.ascontiguousarray(np.concatenate([i for i, _ in rows]) if rows else np.zeros(0), dtype=np.int32)
+    val = np.ascontiguousarray(np.concatenate([v for _, v in rows]) if rows else np.zeros(0), dtype=np.float64)
+    return ptr, idx, val
 
 
 def _obs(z):
@@ -686,6 +716,71 @@ class EKFSlamState(SlamState):
             return new_index
 
         return merge_in_batches(self.N, pairs, call)
+
+    # -- caller-supplied models (libslamhip_linear.so, include/ext/slamhip_linear.h) ------------------------------------
+    def _linear(self, fn, H, z, R, wrap, innovation):
+        ptr, idx, val = linear_rows(H, self.n)
+        k = ptr.size - 1
+        zz = _dbl(z, k)
+        Rm = np.asarray(R, dtype=np.float64)
+        if Rm.ndim < 2:                                                   # a scalar (k = 1) or the diagonal
+            Rm = np.diag(np.broadcast_to(Rm.reshape(-1), (k,)).astype(np.float64))
+        if Rm.shape != (k, k):
+            raise ValueError(f"R must be {k} x {k}")
+        rr = np.ascontiguousarray(Rm.T).reshape(-1)                       # column-major
+        mask = 0
+        for i in wrap:
+            if not 0 <= int(i) < k:
+                raise ValueError("wrap names a row that does not exist")
+            mask |= 1 << int(i)
+        out = np.zeros(4)
+        mode = _lib.SLAM_LINEAR_INNOVATION if innovation else _lib.SLAM_LINEAR_MEASURED
+        check(fn(self._h, k, _ptr(ptr, C.c_int32), _ptr(idx, C.c_int32), _ptr(val), _ptr(zz), _ptr(rr), mode, mask, _ptr(out)))
+        return out
+
+    def update_linear(self, H, z, R, wrap=(), innovation=False):
+        """The Kalman update from a linear measurement z = H x + noise(R), in place on the device (slam_ekf_update_linear): the
+        Cholesky form of ``update`` with the caller's H.  ``H``: a dense (k, n) array or a list of ``{state index: value}`` rows,
+        k <= 16 rows of at most 8 non-zeros; state indices are 0-based (0, 1, 2 the vehicle; landmark j at 3 + 2 (j - 1)).
+        ``R``: k x k, the diagonal, or a scalar.  ``wrap``: the rows whose innovation is an angle (wrapped to [-pi, pi]).
+        ``innovation=True``: ``z`` already IS the innovation of a model the caller linearised.  Returns
+        ``[v' inv(S) v, log det S, smallest pivot, -1]``; raises NotPositiveDefinite with the state unchanged."""
+        return self._linear(_lib.linear_lib().slam_ekf_update_linear, H, z, R, wrap, innovation)
+
+    def linear_nis(self, H, z, R, wrap=(), innovation=False):
+        """What ``update_linear`` would return, with the state only read (slam_ekf_linear_nis): the chi-square gate to apply
+        before committing a fix."""
+        return self._linear(_lib.linear_lib().slam_ekf_linear_nis, H, z, R, wrap, innovation)
+
+    def predict_linear(self, xv, Gv, Qv):
+        """Predict with a caller's motion model (slam_ekf_predict_linear): x[0:3] = xv, P_vv = Gv P_vv Gv' + Qv,
+        P_vm = Gv P_vm.  Of Qv the lower triangle is read."""
+        a, g, q = _dbl(xv, 3), _mat3(Gv), _mat3(Qv)
+        check(_lib.linear_lib().slam_ekf_predict_linear(self._h, _ptr(a), _ptr(g), _ptr(q)))
+
+    def predict_odometry(self, d, Q3):
+        """Compose the pose with a vehicle-frame increment d = (dx, dy, dtheta) of covariance Q3, wholly on the device
+        (slam_ekf_predict_odometry): wheel odometry of any drive."""
+        a, q = _dbl(d, 3), _mat3(Q3)
+        check(_lib.linear_lib().slam_ekf_predict_odometry(self._h, _ptr(a), _ptr(q)))
+
+    def fix_position(self, xy, R):
+        """A position fix (a GPS receiver): the vehicle is at ``xy`` with covariance ``R``."""
+        return self.update_linear([{0: 1.0}, {1: 1.0}], xy, R)
+
+    def fix_heading(self, phi, var):
+        """A heading fix (a compass): the heading is ``phi`` with variance ``var``; the innovation is wrapped."""
+        return self.update_linear([{2: 1.0}], [phi], var, wrap=(0,))
+
+    def fix_landmark(self, j, xy, R):
+        """Landmark ``j`` (1-based) was surveyed at ``xy`` with covariance ``R``."""
+        f = 3 + 2 * (int(j) - 1)
+        return self.update_linear([{f: 1.0}, {f + 1: 1.0}], xy, R)
+
+    def constrain_landmarks(self, a, b, dxy, R):
+        """Landmark ``b`` lies ``dxy`` from landmark ``a`` (1-based), with covariance ``R`` (0: exactly)."""
+        fa, fb = 3 + 2 * (int(a) - 1), 3 + 2 * (int(b) - 1)
+        return self.update_linear([{fb: 1.0, fa: -1.0}, {fb + 1: 1.0, fa + 1: -1.0}], dxy, R)
 
     def transform(self, tx, ty, theta):
         """Express the whole state in another frame, in place on the device (slam_ekf_transform): every position becomes

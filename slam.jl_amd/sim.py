@@ -147,6 +147,7 @@ class SimLog:
     nees_truth: list = field(default_factory=list)      # the true state each sample was held against (pose, then the map's landmarks)
     landmark_tags: object = None                        # sim(nees_every=k): 1-based true landmark behind each map landmark at the end
     best_path: object = None                            # [L, 3]: the best particle's path at the end of the run (a PFSlamState after track_path)
+    fixes: list = field(default_factory=list)           # (predict-step index, measured xy) per position fix (sim(fix_every=k))
 
 
 #: constants of sim/ekfslam-sim.jl:62-76,114
@@ -169,7 +170,8 @@ def default_QR():
 
 def sim(filt, waypoints: np.ndarray, landmarks: np.ndarray, seed: int, nlaps: int = 2,
         max_steps: int = 100000, monitor=None, fused: bool = False, prune_after=None, merge_gate=None,
-        submap_steps=None, association: str = "nearest", nees_every=None) -> SimLog:
+        submap_steps=None, association: str = "nearest", nees_every=None, fix_every: int = 0,
+        fix_sigma: float = 0.5) -> SimLog:
     """The loop of sim/ekfslam-sim.jl:80-141 without sleep/pause.
 
     ``filt`` must already hold the initial state (x = initial pose, P = 0).
@@ -200,7 +202,14 @@ def sim(filt, waypoints: np.ndarray, landmarks: np.ndarray, seed: int, nlaps: in
     created it (the sensor's tags, which the filter never sees, are carried here through every new feature, removal and merge; a
     merged landmark keeps the tag of its lowest old id).  A wrong association therefore counts against the filter, as it should.
     A matrix that has no Cholesky factor is recorded as NaN.  Not available with ``submap_steps`` (the truth is in another frame there).
+    ``fix_every``: 0 (default) changes nothing.  An integer k (no counterpart in the reference): at the end of every k-th step a
+    position fix -- the true position plus noise of standard deviation ``fix_sigma`` per axis, a GPS receiver -- is applied with
+    ``filt.fix_position(xy, fix_sigma^2 I)``.  Its noise comes from a generator of its own (seeded from ``seed``), so every other
+    draw of the run is what it is without fixes.  Fixes are recorded in ``log.fixes``.  Not available with ``submap_steps``.
     """
+    fix_every = int(fix_every)
+    if fix_every < 0 or (fix_every and submap_steps is not None):
+        raise ValueError("fix_every must be a non-negative step count and is not available with submap_steps")
     if association not in ("nearest", "joint"):
         raise ValueError('association must be "nearest" or "joint"')
     joint = association == "joint"
@@ -213,6 +222,7 @@ def sim(filt, waypoints: np.ndarray, landmarks: np.ndarray, seed: int, nlaps: in
             raise ValueError("prune_after counts matches in one map: not available with submap_steps")
         return _sim_submaps(filt, waypoints, landmarks, seed, nlaps, max_steps, monitor, fused, merge_gate, int(submap_steps))
     rng = np.random.default_rng(seed)
+    fix_rng = np.random.default_rng([int(seed), 0x6669]) if fix_every else None
     Q, R = default_QR()
     vehicle = Vehicle(pose=initial_pose(waypoints))
     log = SimLog()
@@ -280,6 +290,10 @@ def sim(filt, waypoints: np.ndarray, landmarks: np.ndarray, seed: int, nlaps: in
                         np.maximum.at(nhits, new_index - 1, hits)
                         born, hits = nborn, nhits
         nsteps += 1
+        if fix_every and nsteps % fix_every == 0:
+            xy = np.asarray(vehicle.pose[:2], dtype=float) + fix_rng.standard_normal(2) * float(fix_sigma)
+            filt.fix_position(xy, np.eye(2) * float(fix_sigma) ** 2)
+            log.fixes.append((nsteps, xy))
         log.true_track.append(np.array(vehicle.pose))
         log.slam_track.append(np.array(filt.pose()))
         if nees_every is not None and nsteps % int(nees_every) == 0:
