@@ -20,7 +20,8 @@ export SlamState, EKFSlamState, set_state!, predict, update, add_features, assoc
        resample!, mean_pose, weights, particles, pf_map, pf_best_particle, to_ekf, to_particles, peer_blob, attach_peers!, peer_selftest, detach_peers!, comm_info,
        upload!, resize, pose_bins, kld_particle_count, pf_meta, set_rng!,
        CovFactor, factor, factor!, logdet, isposdef, whiten, nees, sample,
-       update_linear!, linear_nis, predict_linear!, predict_odometry!, fix_position!, fix_heading!, fix_landmark!
+       update_linear!, linear_nis, predict_linear!, predict_odometry!, fix_position!, fix_heading!, fix_landmark!,
+       step_proposal_unknown!, associate_proposal, proposal_max_obs
 
 const libslamhip = get(ENV, "SLAMHIP_LIB", joinpath(@__DIR__, "libslamhip.so"))
 # the companion library of include/slamhip_frame.h (the rigid frame change); it links against libslamhip.so and lies beside it
@@ -54,6 +55,9 @@ const libslamhip_factor = get(ENV, "SLAMHIP_FACTOR_LIB", joinpath(@__DIR__, "lib
 # the extension library of include/ext/slamhip_linear.h (caller-supplied motion and measurement models for the EKF), same
 # arrangement (opened at the first update_linear! / linear_nis / predict_linear! / predict_odometry!)
 const libslamhip_linear = get(ENV, "SLAMHIP_LINEAR_LIB", joinpath(@__DIR__, "libslamhip_linear.so"))
+# the extension library of include/ext/slamhip_proposal.h (FastSLAM 2.0 with unknown correspondences), same arrangement (opened at
+# the first step_proposal_unknown! / associate_proposal / proposal_max_obs)
+const libslamhip_proposal = get(ENV, "SLAMHIP_PROPOSAL_LIB", joinpath(@__DIR__, "libslamhip_proposal.so"))
 
 const SLAM_OK = Cint(0)
 const SLAM_PF_HALTED = Cint(1)
@@ -917,6 +921,48 @@ function step_unknown!(s::PFSlamState, V::Real, G::Real, wheelbase::Real, Q::Abs
                 s.handle, V, G, wheelbase, colmajor4(Q), dt, pairs64(z), size(z, 2), colmajor4(R), gate1, gate2,
                 Ptr{Int32}(C_NULL), out))
     out
+end
+
+"""
+    step_proposal_unknown!(state, V, G, wheelbase, Q, dt, z, R, gate1, gate2; d_assoc = C_NULL) -> [max logw, sum, sum2]
+
+FastSLAM 2.0 with UNKNOWN correspondences (slam_pf_step_proposal_unknown, include/ext/slamhip_proposal.h): every particle
+associates the (range, bearing) pairs `z` (2 x m, m <= proposal_max_obs()) with its own landmarks under the prior proposal, draws
+its pose from the proposal that knows the matched ones and updates its map from the sampled pose.  `Q` is any symmetric positive
+definite 2 x 2 matrix.  `d_assoc`: a DEVICE array ([m][n] Int32) that receives the decisions (slot >= 0, -1 new, -2 dropped).
+Whole filter on one shard; the call synchronises.
+"""
+function step_proposal_unknown!(s::PFSlamState, V::Real, G::Real, wheelbase::Real, Q::AbstractMatrix, dt::Real, z::AbstractMatrix,
+                                R::AbstractMatrix, gate1::Real, gate2::Real; d_assoc::Ptr{Int32} = Ptr{Int32}(C_NULL))
+    out = zeros(Float64, 3)
+    check(ccall((:slam_pf_step_proposal_unknown, libslamhip_proposal), Cint,
+                (Ptr{Cvoid}, Cdouble, Cdouble, Cdouble, Ptr{Cdouble}, Cdouble, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cdouble, Cdouble,
+                 Ptr{Int32}, Ptr{Cdouble}),
+                s.handle, V, G, wheelbase, colmajor4(Q), dt, pairs64(z), size(z, 2), colmajor4(R), gate1, gate2, d_assoc, out))
+    out
+end
+
+"""
+    associate_proposal(state, V, G, wheelbase, Q, dt, z, R, gate1, gate2, d_assoc; d_nis = C_NULL)
+
+The association of `step_proposal_unknown!` alone (slam_pf_associate_proposal): the state is only read.  `d_assoc` ([m][n] Int32)
+and `d_nis` ([m][n] in the state's element type: the nis of the winning slot, NaN where nothing matched) are DEVICE arrays; the
+call is enqueued on the filter's stream.
+"""
+function associate_proposal(s::PFSlamState, V::Real, G::Real, wheelbase::Real, Q::AbstractMatrix, dt::Real, z::AbstractMatrix,
+                            R::AbstractMatrix, gate1::Real, gate2::Real, d_assoc::Ptr{Int32}; d_nis::Ptr{Cvoid} = C_NULL)
+    check(ccall((:slam_pf_associate_proposal, libslamhip_proposal), Cint,
+                (Ptr{Cvoid}, Cdouble, Cdouble, Cdouble, Ptr{Cdouble}, Cdouble, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cdouble, Cdouble,
+                 Ptr{Int32}, Ptr{Cvoid}),
+                s.handle, V, G, wheelbase, colmajor4(Q), dt, pairs64(z), size(z, 2), colmajor4(R), gate1, gate2, d_assoc, d_nis))
+    s
+end
+
+"Observations per call of `step_proposal_unknown!`, as the library reports it (slam_pf_proposal_limits)."
+function proposal_max_obs()
+    out = zeros(Cint, 4)
+    check(ccall((:slam_pf_proposal_limits, libslamhip_proposal), Cint, (Ptr{Cint},), out))
+    Int(out[1])
 end
 
 """

@@ -357,6 +357,27 @@ LINEAR_SIGNATURES = {
 linear_lib = Companion("linear", LINEAR_SIGNATURES)
 LINEAR_LIB_PATH = linear_lib.path
 
+# ---- proposal: FastSLAM 2.0 with unknown correspondences, opened at the first such step -------------------------------------------
+# Wired like linear, and like it entered in neither table; its surface checks are made by tests/test_proposal_unknown_ref_cpu.py.
+#: every symbol include/ext/slamhip_proposal.h declares
+PROPOSAL_SIGNATURES = {
+    "slam_pf_step_proposal_unknown": (C.c_int, [_h, C.c_double, C.c_double, C.c_double, _dp, C.c_double, _dp, C.c_int, _dp,
+                                                C.c_double, C.c_double, C.c_void_p, _dp]),
+    "slam_pf_associate_proposal": (C.c_int, [_h, C.c_double, C.c_double, C.c_double, _dp, C.c_double, _dp, C.c_int, _dp,
+                                             C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
+    "slam_pf_proposal_limits": (C.c_int, [C.POINTER(C.c_int)]),
+}
+
+proposal_lib = Companion("proposal", PROPOSAL_SIGNATURES)
+PROPOSAL_LIB_PATH = proposal_lib.path
+
+
+def proposal_max_obs() -> int:
+    """Observations per call of the proposal step with unknown correspondences, as the library reports it."""
+    out = (C.c_int * 4)()
+    check(proposal_lib().slam_pf_proposal_limits(out))
+    return int(out[0])
+
 
 def last_error() -> str:
     msg = lib.slam_last_error()

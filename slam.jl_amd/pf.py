@@ -28,7 +28,7 @@ import sys
 
 import numpy as np
 
-from ._lib import SLAM_F32, SLAM_F64, SLAM_PF_HALTED, SLAM_PF_PEER_BLOB_BYTES, check, evidence_lib, frame_lib, handover_lib, lib, path_lib, pfcopy_lib
+from ._lib import SLAM_F32, SLAM_F64, SLAM_PF_HALTED, SLAM_PF_PEER_BLOB_BYTES, check, evidence_lib, frame_lib, handover_lib, lib, path_lib, pfcopy_lib, proposal_lib
 from .ekf import EKFSlamState, _obs, _small, _ptr, rigid_fit
 
 __all__ = ["PFShard", "PFSlamState", "FastSLAM", "LandmarkEvidence", "PathHistory", "philox_uniform", "small", "shared_page", "attach_local_peers",
@@ -230,6 +230,44 @@ class PFShard:
                                        float(gate1), float(gate2), ptr, _ptr(out)))
         stats = (float(out[0]), float(out[1]), float(out[2]))      # (the call synchronises: assoc is complete)
         return (stats, assoc) if want_assoc else stats
+
+    def step_proposal_unknown(self, V, G, wheelbase, Q, dt, z, R, gate1, gate2, want_assoc=False):
+        """FastSLAM 2.0 with unknown correspondences (slam_pf_step_proposal_unknown, include/ext/slamhip_proposal.h): every
+        particle associates the at most 16 observations with its own landmarks under the prior proposal, draws its pose from
+        the proposal that knows the matched ones, and updates its map from the sampled pose.  Whole filter on this shard.
+        Returns (gmax, s1, s2), or ((gmax, s1, s2), assoc) with ``want_assoc`` (int32 torch tensor [m, n] on the device:
+        slot >= 0 matched, -1 new, -2 dropped)."""
+        zp = _obs(z)
+        m = zp.shape[0]
+        q, r = _small(Q), _small(R)
+        assoc = None
+        ptr = None
+        if want_assoc:
+            import torch
+            assoc = torch.empty((m, self.n), dtype=torch.int32, device=self.device)
+            ptr = C.c_void_p(assoc.data_ptr()) if m else None
+        out = np.empty(3)
+        check(proposal_lib().slam_pf_step_proposal_unknown(self._h, float(V), float(G), float(wheelbase), _ptr(q), float(dt),
+                                                           _ptr(zp), m, _ptr(r), float(gate1), float(gate2), ptr, _ptr(out)))
+        stats = (float(out[0]), float(out[1]), float(out[2]))      # (the call synchronises: assoc is complete)
+        return (stats, assoc) if want_assoc else stats
+
+    def associate_proposal(self, V, G, wheelbase, Q, dt, z, R, gate1, gate2, want_nis=False):
+        """The association of ``step_proposal_unknown`` alone (slam_pf_associate_proposal): the state is only read.  Returns
+        the decisions (int32 torch tensor [m, n] on the device), or (decisions, nis) with ``want_nis``: the nis of the winning
+        slot in the shard's dtype, NaN where nothing matched."""
+        import torch
+        zp = _obs(z)
+        m = zp.shape[0]
+        q, r = _small(Q), _small(R)
+        assoc = torch.empty((m, self.n), dtype=torch.int32, device=self.device)
+        nis = torch.empty((m, self.n), dtype=self.torch_dtype, device=self.device) if want_nis else None
+        check(proposal_lib().slam_pf_associate_proposal(self._h, float(V), float(G), float(wheelbase), _ptr(q), float(dt),
+                                                        _ptr(zp), m, _ptr(r), float(gate1), float(gate2),
+                                                        C.c_void_p(assoc.data_ptr()) if m else None,
+                                                        C.c_void_p(nis.data_ptr()) if (want_nis and m) else None))
+        self.sync()
+        return (assoc, nis) if want_nis else assoc
 
     def weight_stats(self):
         out = np.empty(3)
@@ -1118,14 +1156,20 @@ class FastSLAM:
         self.resample()                                   # the legacy path: collectives issued from here
         sh.resume(self.resamples)
 
-    def step_unknown(self, V, G, wheelbase, Q, dt, z, R, gate1, gate2, force_resample=None):
+    def step_unknown(self, V, G, wheelbase, Q, dt, z, R, gate1, gate2, force_resample=None, proposal=False):
         """The filter step with UNKNOWN correspondences: predict, per-particle gated nearest-neighbour
         association + updates / new landmarks, normalise, (Neff-triggered) resample.  Returns (Neff, resampled?).
-        Resampling copies whole particle records, unused landmark slots included, so it needs no change."""
+        Resampling copies whole particle records, unused landmark slots included, so it needs no change.
+        ``proposal``: the FastSLAM-2.0 form (shard.step_proposal_unknown: association under the proposal, the pose drawn
+        from the proposal that knows the matched observations); at most 16 observations, whole filter on one rank."""
         self._gmax_norm = None
-        self.predict(V, G, wheelbase, Q, dt)
-        self.shard.update_unknown(z, R, gate1, gate2)
-        neff = self.normalize()
+        if proposal:
+            assert self.comm.world == 1, "the proposal step with unknown correspondences needs the whole filter on one rank"
+            neff = self.normalize(self.shard.step_proposal_unknown(V, G, wheelbase, Q, dt, z, R, gate1, gate2))
+        else:
+            self.predict(V, G, wheelbase, Q, dt)
+            self.shard.update_unknown(z, R, gate1, gate2)
+            neff = self.normalize()
         do = force_resample if force_resample is not None else (neff < self.neff_frac * self.shard.n_global)
         if do:
             self.resample()
@@ -1143,16 +1187,21 @@ class FastSLAM:
         self._record_path()
         return neff, bool(do)
 
-    def step_unknown_pruned(self, V, G, wheelbase, Q, dt, z, R, gate1, gate2, evidence, force_resample=None):
+    def step_unknown_pruned(self, V, G, wheelbase, Q, dt, z, R, gate1, gate2, evidence, force_resample=None, proposal=False):
         """``step_unknown_fused`` with landmark evidence: the step is taken through ``evidence.step`` (a
         :class:`LandmarkEvidence` of this filter's shard: association + updates / new landmarks, then the counters and the
         pruning), and a resampling goes through ``evidence.resample`` so that the counters follow their particles.  Pruning
         touches no weight.  Whole filter on one rank only.  Returns (Neff, resampled?, counts) with counts = [records in
-        use, created, decremented, pruned] of this step."""
+        use, created, decremented, pruned] of this step.  ``proposal``: the step is shard.step_proposal_unknown (FastSLAM 2.0,
+        at most 16 observations), followed by ``evidence.update`` on its decisions."""
         assert self.comm.world == 1, "landmark evidence supports only a filter that lives wholly on one rank"
         self._no_path("step_unknown_pruned")
         self._gmax_norm = None
-        stats, counts = evidence.step(V, G, wheelbase, Q, dt, z, R, gate1, gate2)
+        if proposal:
+            stats, assoc = self.shard.step_proposal_unknown(V, G, wheelbase, Q, dt, z, R, gate1, gate2, want_assoc=True)
+            counts = evidence.update(assoc, assume_ready=True)
+        else:
+            stats, counts = evidence.step(V, G, wheelbase, Q, dt, z, R, gate1, gate2)
         neff = self.normalize(stats)
         do = force_resample if force_resample is not None else (neff < self.neff_frac * self.shard.n_global)
         if do:
