@@ -56,6 +56,43 @@ struct SlamRange {
 #define SLAM_KPAD 32
 
 static inline int round_up(int a, int b) { return (a + b - 1) / b * b; }
+// the offsets inside one scratch allocation: every array starts on a 256-byte boundary
+static inline size_t slam_align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// ---- allocation ---------------------------------------------------------------
+// *p <- `bytes` of device memory (at least 16), zeroed on stream s; *p is null after a failure
+template <typename P>
+inline int slam_alloc_zero(P** p, size_t bytes, hipStream_t s) {
+    *p = nullptr;
+    if (bytes == 0) bytes = 16;
+    HIP_TRY(hipMalloc((void**)p, bytes));
+    HIP_TRY(hipMemsetAsync(*p, 0, bytes, s));
+    return SLAM_OK;
+}
+
+// ---- two streams around work on one of them ------------------------------------
+// `body` enqueues on sd work that reads what ss has produced: sd waits for everything enqueued on ss so far, and ss waits for
+// what body enqueued, so that the owner of ss cannot overwrite what is still being read.  After a failed body the second pair
+// still runs (ss never overtakes what WAS enqueued); body's error takes precedence over the event calls'.
+template <typename F>
+int slam_between(hipStream_t sd, hipStream_t ss, F body) {
+    hipEvent_t es = nullptr, ed = nullptr;
+    HIP_TRY(hipEventCreateWithFlags(&es, hipEventDisableTiming));
+    hipError_t e = hipEventCreateWithFlags(&ed, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventRecord(es, ss);
+    if (e == hipSuccess) e = hipStreamWaitEvent(sd, es, 0);              // behind everything enqueued on ss
+    int rc = SLAM_OK;
+    if (e == hipSuccess) {
+        rc = body();
+        e = hipEventRecord(ed, sd);                                      // the last read of ss's data lies before this
+        if (e == hipSuccess) e = hipStreamWaitEvent(ss, ed, 0);
+    }
+    (void)hipEventDestroy(es);                                            // (released by the runtime once they have completed)
+    if (ed) (void)hipEventDestroy(ed);
+    if (rc) return rc;
+    HIP_TRY(e);
+    return SLAM_OK;
+}
 
 // A/B knobs of the measurement tooling (tile order, workgroups per list, super-row height, the scalar factorisation ...):
 // read from the environment ONLY in the experiments build (`make exp`, libslamhip_exp.so); the product library always

@@ -109,15 +109,6 @@ static int fold_timing(slam_ekf* h) {
 }
 
 // ---- allocation helpers --------------------------------------------------------
-template <typename P>
-static int dev_alloc_zero(P** p, size_t bytes, hipStream_t s) {
-    *p = nullptr;
-    if (bytes == 0) bytes = 16;
-    HIP_TRY(hipMalloc((void**)p, bytes));
-    HIP_TRY(hipMemsetAsync(*p, 0, bytes, s));
-    return SLAM_OK;
-}
-
 static void dev_free(void* p) {
     if (p) (void)hipFree(p);
 }
@@ -135,15 +126,15 @@ int ensure_obs_capacity(slam_ekf* h, int nobs) {
     h->h_obs = nullptr; h->h_idf = nullptr; h->h_assoc = nullptr;
     h->ocap = 0;
     int rc;
-    if ((rc = dev_alloc_zero(&h->obsbuf, sizeof(double) * 2 * cap, h->stream))) return rc;
-    if ((rc = dev_alloc_zero(&h->idfbuf, sizeof(int32_t) * cap, h->stream))) return rc;
-    if ((rc = dev_alloc_zero(&h->d_assoc, sizeof(int32_t) * cap, h->stream))) return rc;
-    if ((rc = dev_alloc_zero(&h->znbuf, sizeof(double) * 2 * cap, h->stream))) return rc;
+    if ((rc = slam_alloc_zero(&h->obsbuf, sizeof(double) * 2 * cap, h->stream))) return rc;
+    if ((rc = slam_alloc_zero(&h->idfbuf, sizeof(int32_t) * cap, h->stream))) return rc;
+    if ((rc = slam_alloc_zero(&h->d_assoc, sizeof(int32_t) * cap, h->stream))) return rc;
+    if ((rc = slam_alloc_zero(&h->znbuf, sizeof(double) * 2 * cap, h->stream))) return rc;
     // the sweep's candidate lists: per chunk of 128 observations [128][gate_blocks_cap] entries of 2 doubles {nd, landmark},
     // then two int32 words per observation (cnt, near): 256 * cap + 128 doubles, inside the 768 * cap allocated here.
     // At most one entry per workgroup per observation, and cap >= ceil(maxN / 64) workgroups: a list cannot overflow.
     h->gate_blocks_cap = (h->maxN + 63) / 64 + 1;
-    if ((rc = dev_alloc_zero(&h->gate_part, sizeof(double) * 3 * 256 * (size_t)h->gate_blocks_cap, h->stream))) return rc;
+    if ((rc = slam_alloc_zero(&h->gate_part, sizeof(double) * 3 * 256 * (size_t)h->gate_blocks_cap, h->stream))) return rc;
     HIP_TRY(hipHostMalloc((void**)&h->h_obs, sizeof(double) * 2 * cap, hipHostMallocDefault));
     HIP_TRY(hipHostMalloc((void**)&h->h_idf, sizeof(int32_t) * cap, hipHostMallocDefault));
     HIP_TRY(hipHostMalloc((void**)&h->h_assoc, sizeof(int32_t) * cap, hipHostMallocDefault));
@@ -178,16 +169,16 @@ int ensure_update_workspace(slam_ekf* h, int m) {
     HIP_TRY(hipStreamSynchronize(h->stream));
     free_update_workspace(h);
     int rc;
-    if ((rc = dev_alloc_zero(&h->PHt, sizeof(double) * (size_t)h->npad * cap, h->stream))) return rc;
-    if ((rc = dev_alloc_zero(&h->PHtS, sizeof(double) * (size_t)(3 + cap) * cap, h->stream))) return rc;
-    if ((rc = dev_alloc_zero(&h->Kd, sizeof(double) * (size_t)h->npad * cap, h->stream))) return rc;
-    if ((rc = dev_alloc_zero(&h->W1, h->esz * (size_t)h->npad * 2 * cap, h->stream))) return rc;
-    if ((rc = dev_alloc_zero(&h->W2, h->esz * (size_t)h->npad * 2 * cap, h->stream))) return rc;
-    if (h->dtype == SLAM_F32 && (rc = dev_alloc_zero(&h->Wimg, (size_t)(h->npad / 128) * (cap / 16) * 3 * 4096, h->stream))) return rc;
-    if ((rc = dev_alloc_zero(&h->Cmat, sizeof(double) * (size_t)cap * cap, h->stream))) return rc;
-    if ((rc = dev_alloc_zero(&h->Smat, sizeof(double) * (size_t)cap * cap, h->stream))) return rc;
-    if ((rc = dev_alloc_zero(&h->Mwork, sizeof(double) * (size_t)cap * (cap + 1), h->stream))) return rc;
-    if ((rc = dev_alloc_zero(&h->gvec, sizeof(double) * (size_t)cap, h->stream))) return rc;
+    if ((rc = slam_alloc_zero(&h->PHt, sizeof(double) * (size_t)h->npad * cap, h->stream))) return rc;
+    if ((rc = slam_alloc_zero(&h->PHtS, sizeof(double) * (size_t)(3 + cap) * cap, h->stream))) return rc;
+    if ((rc = slam_alloc_zero(&h->Kd, sizeof(double) * (size_t)h->npad * cap, h->stream))) return rc;
+    if ((rc = slam_alloc_zero(&h->W1, h->esz * (size_t)h->npad * 2 * cap, h->stream))) return rc;
+    if ((rc = slam_alloc_zero(&h->W2, h->esz * (size_t)h->npad * 2 * cap, h->stream))) return rc;
+    if (h->dtype == SLAM_F32 && (rc = slam_alloc_zero(&h->Wimg, (size_t)(h->npad / 128) * (cap / 16) * 3 * 4096, h->stream))) return rc;
+    if ((rc = slam_alloc_zero(&h->Cmat, sizeof(double) * (size_t)cap * cap, h->stream))) return rc;
+    if ((rc = slam_alloc_zero(&h->Smat, sizeof(double) * (size_t)cap * cap, h->stream))) return rc;
+    if ((rc = slam_alloc_zero(&h->Mwork, sizeof(double) * (size_t)cap * (cap + 1), h->stream))) return rc;
+    if ((rc = slam_alloc_zero(&h->gvec, sizeof(double) * (size_t)cap, h->stream))) return rc;
     h->kcap = cap;
     return SLAM_OK;
 }
@@ -269,25 +260,25 @@ static int create_impl(slam_ekf* h) {
     int rc;
     if ((rc = update_kernels_init())) return rc;
     if ((rc = gate_kernels_init())) return rc;
-    if ((rc = dev_alloc_zero(&h->x, h->esz * (size_t)h->ncap, h->stream))) return rc;
+    if ((rc = slam_alloc_zero(&h->x, h->esz * (size_t)h->ncap, h->stream))) return rc;
     {   // tile-major, block lower (device_math.h): T (T + 1) / 2 tiles of E x E elements
         const int E = h->dtype == SLAM_F32 ? 128 : 64;
         const size_t T = (size_t)h->npad / E;
-        if ((rc = dev_alloc_zero(&h->P, h->esz * (T * (T + 1) / 2) * E * E, h->stream))) return rc;
-        if ((rc = dev_alloc_zero(&h->Pside, h->esz * 3 * (size_t)(h->npad / 2), h->stream))) return rc;
+        if ((rc = slam_alloc_zero(&h->P, h->esz * (T * (T + 1) / 2) * E * E, h->stream))) return rc;
+        if ((rc = slam_alloc_zero(&h->Pside, h->esz * 3 * (size_t)(h->npad / 2), h->stream))) return rc;
     }
-    if ((rc = dev_alloc_zero(&h->d_small, sizeof(double) * 64, h->stream))) return rc;
-    if ((rc = dev_alloc_zero(&h->d_count, sizeof(int32_t) * 4, h->stream))) return rc;
-    if ((rc = dev_alloc_zero(&h->d_pmax, sizeof(double), h->stream))) return rc;
-    if ((rc = dev_alloc_zero(&h->dd_claim, 8 * 64, h->stream))) return rc;
+    if ((rc = slam_alloc_zero(&h->d_small, sizeof(double) * 64, h->stream))) return rc;
+    if ((rc = slam_alloc_zero(&h->d_count, sizeof(int32_t) * 4, h->stream))) return rc;
+    if ((rc = slam_alloc_zero(&h->d_pmax, sizeof(double), h->stream))) return rc;
+    if ((rc = slam_alloc_zero(&h->dd_claim, 8 * 64, h->stream))) return rc;
     HIP_TRY(hipHostMalloc((void**)&h->h_flag, sizeof(int32_t) * 16, hipHostMallocDefault));
     h->h_flag[0] = 0;
     HIP_TRY(hipHostGetDevicePointer((void**)&h->h_flag_dev, h->h_flag, 0));
-    if ((h->debug_flags & 8) && (rc = dev_alloc_zero(&h->dd_prof, (size_t)4096 * 4 * 4 * 8, h->stream))) return rc;
+    if ((h->debug_flags & 8) && (rc = slam_alloc_zero(&h->dd_prof, (size_t)4096 * 4 * 4 * 8, h->stream))) return rc;
 #ifdef SLAMHIP_EXPERIMENTS
-    if (!h->dd_prof && slam_exp_env("SLAMHIP_STAMPS", 0) && (rc = dev_alloc_zero(&h->dd_prof, (size_t)4096 * 16 * 8, h->stream))) return rc;
+    if (!h->dd_prof && slam_exp_env("SLAMHIP_STAMPS", 0) && (rc = slam_alloc_zero(&h->dd_prof, (size_t)4096 * 16 * 8, h->stream))) return rc;
 #endif
-    if ((rc = dev_alloc_zero(&h->d_status, sizeof(int32_t) * 4, h->stream))) return rc;
+    if ((rc = slam_alloc_zero(&h->d_status, sizeof(int32_t) * 4, h->stream))) return rc;
     HIP_TRY(hipHostMalloc((void**)&h->h_small, sizeof(double) * 64, hipHostMallocDefault));
     HIP_TRY(hipHostMalloc((void**)&h->h_status, sizeof(int32_t) * 4, hipHostMallocDefault));
     if ((rc = ensure_obs_capacity(h, 256))) return rc;

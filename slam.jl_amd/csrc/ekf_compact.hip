@@ -46,7 +46,7 @@ template <typename T>
 __global__ __launch_bounds__(256) void compact_gather_kernel(const T* __restrict__ P, T* __restrict__ stage,
                                                               const int32_t* __restrict__ keep, int ld, int n_new, int I0, int I1,
                                                               int J0) {
-    constexpr int L = sizeof(T) == 4 ? 7 : 6;                   // tile edge 128 (fp32) / 64 (fp64)
+    constexpr int L = kTileLog2<T>;                   // tile edge 128 (fp32) / 64 (fp64)
     constexpr int E = 1 << L, m = E - 1;
     const int J = J0 + blockIdx.y;
     const int I = (J > I0 ? J : I0) + blockIdx.x;
@@ -112,7 +112,7 @@ __global__ __launch_bounds__(256) void compact_gather_kernel(const T* __restrict
 template <typename T>
 __global__ __launch_bounds__(256) void compact_store_kernel(T* __restrict__ P, const T* __restrict__ stage, int ld, int I0, int I1,
                                                              int J0) {
-    constexpr int L = sizeof(T) == 4 ? 7 : 6;
+    constexpr int L = kTileLog2<T>;
     const int J = J0 + blockIdx.y;
     const int I = (J > I0 ? J : I0) + blockIdx.x;
     if (I > I1) return;

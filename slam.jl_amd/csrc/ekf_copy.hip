@@ -61,18 +61,6 @@ __device__ __forceinline__ void mv_store(V v, V* p) {
 #endif
 }
 
-// tile q of the Tw (Tw + 1) / 2 tiles of the leading Tw tile rows, numbered band after band: base(J) = J Tw - J (J - 1) / 2
-__device__ __forceinline__ void tile_of(long long q, int Tw, int* I, int* J) {
-    const double b = 2.0 * Tw + 1.0;
-    int j = (int)((b - sqrt(b * b - 8.0 * (double)q)) * 0.5);
-    if (j < 0) j = 0;
-    if (j > Tw - 1) j = Tw - 1;
-    while (j > 0 && (long long)j * Tw - (long long)j * (j - 1) / 2 > q) --j;
-    while (j < Tw - 1 && (long long)(j + 1) * Tw - (long long)(j + 1) * j / 2 <= q) ++j;
-    *J = j;
-    *I = j + (int)(q - ((long long)j * Tw - (long long)j * (j - 1) / 2));
-}
-
 // source state index of destination index i (select); i < n'
 __device__ __forceinline__ int src_index(const int32_t* __restrict__ ids, int i) {
     return i < 3 ? i : 3 + 2 * (ids[(i - 3) >> 1] - 1) + ((i - 3) & 1);
@@ -81,7 +69,7 @@ __device__ __forceinline__ int src_index(const int32_t* __restrict__ ids, int i)
 template <typename T>
 __global__ __launch_bounds__(MOVE_THREADS) void move_tiles_kernel(T* __restrict__ Pd, int ldd, const T* __restrict__ Ps, int lds, int Tw,
                                                                    int Tn, long long items) {
-    constexpr int L = sizeof(T) == 4 ? 7 : 6;
+    constexpr int L = kTileLog2<T>;
     constexpr int S = (1 << L) / SLICE_COLS;                            // slices of a tile
     constexpr int PIECES = SLICE_COLS * (int)sizeof(T) * (1 << L) / 16;   // 16-byte pieces of a slice: 1024
     constexpr int PER = PIECES / MOVE_THREADS;
@@ -108,7 +96,7 @@ __global__ __launch_bounds__(MOVE_THREADS) void move_tiles_kernel(T* __restrict_
 template <typename T>
 __global__ __launch_bounds__(MOVE_THREADS) void gather_tiles_kernel(T* __restrict__ Pd, int ldd, const T* __restrict__ Ps, int lds,
                                                                      const int32_t* __restrict__ ids, int nn, int Tw, long long items) {
-    constexpr int L = sizeof(T) == 4 ? 7 : 6;
+    constexpr int L = kTileLog2<T>;
     constexpr int E = 1 << L;
     constexpr int S = E / SLICE_COLS;
     constexpr int CSTEP = MOVE_THREADS >> L;                             // columns the workgroup covers at a time
@@ -186,7 +174,7 @@ int stage_ids(slam_ekf* dst, const int32_t* ids, int cnt) {
 // everything enqueued on dst's stream; N2: the landmarks dst receives; ids == nullptr: a copy
 template <typename T>
 int move_impl(slam_ekf* dst, const slam_ekf* src, const int32_t* ids, int N2) {
-    constexpr int L = sizeof(T) == 4 ? 7 : 6;
+    constexpr int L = kTileLog2<T>;
     constexpr int E = 1 << L;
     const int nn = 3 + 2 * N2, n_old = 3 + 2 * dst->N;
     const int Td = dst->ld >> L;
@@ -213,36 +201,21 @@ int move_impl(slam_ekf* dst, const slam_ekf* src, const int32_t* ids, int N2) {
     return SLAM_OK;
 }
 
-// the part copy and select share: validated by the caller; ordered against src's stream as slam_ekf_join orders its two maps
+// the part copy and select share: validated by the caller; ordered against src's stream by slam_between (common.h)
 int move_between(slam_ekf* dst, slam_ekf* src, const int32_t* ids, int N2) {
     int rc;
     if (src->pending_status && (rc = slam_ekf_sync(src))) return rc;     // src's deferred status; dst untouched
     HIP_TRY(hipSetDevice(dst->device));
     if (ids && N2 > 0 && (rc = ensure_obs_capacity(dst, N2))) return rc;   // the index buffer and its staging: grow only
-    hipEvent_t es = nullptr, ed = nullptr;
-    HIP_TRY(hipEventCreateWithFlags(&es, hipEventDisableTiming));
-    hipError_t e = hipEventCreateWithFlags(&ed, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventRecord(es, src->stream);
-    if (e == hipSuccess) e = hipStreamWaitEvent(dst->stream, es, 0);     // behind everything enqueued on src
-    rc = SLAM_OK;
-    if (e == hipSuccess) {
-        rc = dst->dtype == SLAM_F32 ? move_impl<float>(dst, src, ids, N2) : move_impl<double>(dst, src, ids, N2);
-        if (rc == SLAM_OK) {
-            // the launches have gone out: the host side follows the device at once, whatever the event calls below return
-            dst->N = N2;
-            dst->grid_force = 1;                                         // the grid belongs to dst's old means
-            dst->pmax_valid = 0;                                         // ... and the variance bound to its old matrix
-            rc = launch_side_rebuild(dst);                               // the packed 2 x 2 diagonal blocks follow the matrix
-        }
-        // (after a failed launch the events still run, so that src never overtakes what was enqueued)
-        e = hipEventRecord(ed, dst->stream);                             // the last read of src lies before this
-        if (e == hipSuccess) e = hipStreamWaitEvent(src->stream, ed, 0);
-    }
-    (void)hipEventDestroy(es);                                            // (released by the runtime once they have completed)
-    if (ed) (void)hipEventDestroy(ed);
-    if (rc) return rc;
-    HIP_TRY(e);
-    return SLAM_OK;
+    return slam_between(dst->stream, src->stream, [&]() -> int {
+        const int rcm = dst->dtype == SLAM_F32 ? move_impl<float>(dst, src, ids, N2) : move_impl<double>(dst, src, ids, N2);
+        if (rcm) return rcm;
+        // the launches have gone out: the host side follows the device at once, whatever the event calls behind them return
+        dst->N = N2;
+        dst->grid_force = 1;                                             // the grid belongs to dst's old means
+        dst->pmax_valid = 0;                                             // ... and the variance bound to its old matrix
+        return launch_side_rebuild(dst);                                 // the packed 2 x 2 diagonal blocks follow the matrix
+    });
 }
 
 int check_pair(slam_ekf* dst, slam_ekf* src) {

@@ -53,34 +53,10 @@ constexpr int DIAG_THREADS = 512;
 constexpr int RHS_MAX = 64;
 constexpr int SOL_THREADS = 1024;
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-
-template <typename T> struct Fx;
-template <> struct Fx<float> {
-    static constexpr int L = 7, MB = 32, KS = 2, NREG = 16, LSH = 5, CB = 32;
-    typedef f32x16 Acc;
-    static __device__ __forceinline__ Acc mfma(float a, float b, Acc c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
-    static __device__ __forceinline__ int out_i(int reg, int half) { return (reg & 3) + 8 * (reg >> 2) + 4 * half; }     // index of the A dimension
+// the MFMA tile (device_math.h) and CB: the columns the panel's triangular solve holds in registers at a time
+template <typename T> struct Fx : MfmaTile<T> {
+    static constexpr int CB = sizeof(T) == 4 ? 32 : 16;
 };
-template <> struct Fx<double> {
-    static constexpr int L = 6, MB = 16, KS = 4, NREG = 4, LSH = 4, CB = 16;
-    typedef f64x4 Acc;
-    static __device__ __forceinline__ Acc mfma(double a, double b, Acc c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
-    static __device__ __forceinline__ int out_i(int reg, int half) { return 4 * reg + half; }
-};
-
-// tile q of the Tw (Tw + 1) / 2 tiles of the leading Tw tile rows, numbered band after band (ekf_copy.hip)
-__device__ __forceinline__ void tile_of(long long q, int Tw, int* I, int* J) {
-    const double b = 2.0 * Tw + 1.0;
-    int j = (int)((b - sqrt(b * b - 8.0 * (double)q)) * 0.5);
-    if (j < 0) j = 0;
-    if (j > Tw - 1) j = Tw - 1;
-    while (j > 0 && (long long)j * Tw - (long long)j * (j - 1) / 2 > q) --j;
-    while (j < Tw - 1 && (long long)(j + 1) * Tw - (long long)(j + 1) * j / 2 <= q) ++j;
-    *J = j;
-    *I = j + (int)(q - ((long long)j * Tw - (long long)j * (j - 1) / 2));
-}
 
 // ---- copy-in: F <- P[0 : n, 0 : n] of the source, every entry of the tiles below Tn (zero outside n) ---------------------------
 // Entry by entry through p_off on both sides (gather_tiles_kernel of ekf_copy.hip), so the two tile edges may differ; the value
@@ -591,28 +567,15 @@ extern "C" int slam_ekf_factor_compute(slam_ekf_factor_t f, slam_ekf_t src, doub
     HIP_TRY(hipSetDevice(f->device));
     const int n = 3 + 2 * src->N;
     f->valid = 0;
-    hipEvent_t es = nullptr, ed = nullptr;
-    HIP_TRY(hipEventCreateWithFlags(&es, hipEventDisableTiming));
-    hipError_t e = hipEventCreateWithFlags(&ed, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventRecord(es, src->stream);
-    if (e == hipSuccess) e = hipStreamWaitEvent(f->stream, es, 0);       // behind everything enqueued on src
-    rc = SLAM_OK;
-    if (e == hipSuccess) {
-        e = hipMemsetAsync(f->stat, 0, sizeof(double) * f->hstat.size(), f->stream);
-        if (e == hipSuccess) {
-            if (f->dtype == SLAM_F32) rc = enqueue_copyin<float, float>(f, src, n);
-            else if (src->dtype == SLAM_F64) rc = enqueue_copyin<double, double>(f, src, n);
-            else rc = enqueue_copyin<double, float>(f, src, n);
-        }
-        // (after a failed launch the events still run, so that src never overtakes what was enqueued)
-        hipError_t e2 = hipEventRecord(ed, f->stream);                   // the last read of src lies before this
-        if (e2 == hipSuccess) e2 = hipStreamWaitEvent(src->stream, ed, 0);
-        if (e == hipSuccess) e = e2;
-    }
-    (void)hipEventDestroy(es);                                            // (released by the runtime once they have completed)
-    if (ed) (void)hipEventDestroy(ed);
+    // the copy-in reads src: ordered against src's stream (after a failed launch the events still run, so that src never overtakes
+    // what was enqueued)
+    rc = slam_between(f->stream, src->stream, [&]() -> int {
+        HIP_TRY(hipMemsetAsync(f->stat, 0, sizeof(double) * f->hstat.size(), f->stream));
+        if (f->dtype == SLAM_F32) return enqueue_copyin<float, float>(f, src, n);
+        if (src->dtype == SLAM_F64) return enqueue_copyin<double, double>(f, src, n);
+        return enqueue_copyin<double, float>(f, src, n);
+    });
     if (rc) return rc;
-    HIP_TRY(e);
     if ((rc = f->dtype == SLAM_F32 ? enqueue_factor<float>(f, n) : enqueue_factor<double>(f, n))) return rc;
     f->hx.resize((size_t)n);
     HIP_TRY(hipMemcpyAsync(f->hx.data(), f->xd, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, f->stream));

@@ -27,67 +27,6 @@ constexpr int GATE_BLOCK = 64;      // landmarks per workgroup (one per lane): N
 constexpr int GATE_WAVES = 1;       // (partials per workgroup and observation)
 constexpr int OBS_WAVES = 8;        // waves per workgroup: all own the same 64 landmarks, wave w the observations w, w+8, ...
 
-struct PairConst {        // per-landmark, observation-independent
-    double zp0, zp1;
-    double s00, s01, s10, s11;
-    double det, logdet;
-    double qa, qb, qc;    // nis = qa*v0^2 + qb*v0*v1 + qc*v1^2  (inv(S) folded in once per landmark)
-};
-
-// S = Hv Pvv Hv' + Hv Pvf Hf' + Hf Pfv Hv' + Hf Pff Hf' + R  (2x2), from the
-// 5x5 sub-block of P.  pvv is row-major 3x3; pfv[a][c] = P[f+a][c]; pff row-major.
-__device__ inline PairConst pair_const(const ObsModel& om, const double* pvv, const double pfv[2][3],
-                                       const double pff[4], const double R[4]) {
-    PairConst pc;
-    pc.zp0 = om.zp[0];
-    pc.zp1 = om.zp[1];
-    double A[2][3];   // Hv * Pvv
-    double B[2][2];   // Hv * Pvf,  Pvf[c][a] = pfv[a][c]
-    double Cc[2][3];  // Hf * Pfv
-    double D[2][2];   // Hf * Pff
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            A[r][c] = om.Hv[r * 3 + 0] * pvv[0 * 3 + c] + om.Hv[r * 3 + 1] * pvv[1 * 3 + c] +
-                      om.Hv[r * 3 + 2] * pvv[2 * 3 + c];
-            Cc[r][c] = om.Hf[r * 2 + 0] * pfv[0][c] + om.Hf[r * 2 + 1] * pfv[1][c];
-        }
-#pragma unroll
-        for (int a = 0; a < 2; ++a) {
-            B[r][a] = om.Hv[r * 3 + 0] * pfv[a][0] + om.Hv[r * 3 + 1] * pfv[a][1] + om.Hv[r * 3 + 2] * pfv[a][2];
-            D[r][a] = om.Hf[r * 2 + 0] * pff[0 * 2 + a] + om.Hf[r * 2 + 1] * pff[1 * 2 + a];
-        }
-    }
-    double S[2][2];
-#pragma unroll
-    for (int r = 0; r < 2; ++r)
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            double s = A[r][0] * om.Hv[q * 3 + 0] + A[r][1] * om.Hv[q * 3 + 1] + A[r][2] * om.Hv[q * 3 + 2];
-            s += B[r][0] * om.Hf[q * 2 + 0] + B[r][1] * om.Hf[q * 2 + 1];
-            s += Cc[r][0] * om.Hv[q * 3 + 0] + Cc[r][1] * om.Hv[q * 3 + 1] + Cc[r][2] * om.Hv[q * 3 + 2];
-            s += D[r][0] * om.Hf[q * 2 + 0] + D[r][1] * om.Hf[q * 2 + 1];
-            S[r][q] = s + R[q * 2 + r];       // R column-major: R[r][q] = R[q*2+r]
-        }
-    pc.s00 = S[0][0]; pc.s01 = S[0][1]; pc.s10 = S[1][0]; pc.s11 = S[1][1];
-    pc.det = pc.s00 * pc.s11 - pc.s01 * pc.s10;
-    pc.logdet = log(pc.det);
-    const double rdet = 1.0 / pc.det;
-    pc.qa = pc.s11 * rdet;
-    pc.qb = -(pc.s01 + pc.s10) * rdet;
-    pc.qc = pc.s00 * rdet;
-    return pc;
-}
-
-// nis = v' inv(S) v  (src/data-association.jl:60), nd = nis + log det S (:61)
-__device__ inline void pair_eval(const PairConst& pc, double z0, double z1, double& nis, double& nd) {
-    const double v0 = z0 - pc.zp0;
-    const double v1 = mpi_to_pi_d(z1 - pc.zp1);        // :57
-    nis = pc.qa * v0 * v0 + pc.qb * v0 * v1 + pc.qc * v1 * v1;
-    nd = nis + pc.logdet;
-}
-
 // side (may be null: the single-pair entry points read the matrix): the packed 2 x 2 diagonal blocks, three coalesced rows
 template <typename T>
 __device__ inline PairConst landmark_const(const T* __restrict__ x, const T* __restrict__ P, int ld, int tlog, int j0,
@@ -424,8 +363,7 @@ __global__ __launch_bounds__(GRID_BUILD_THREADS) void grid_prepare_kernel(const 
             }
             d = __longlong_as_double((long long)m);
         }
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) d += __shfl_xor(d, off);
+        d = wave_sum(d);
         if (lane == 0) {
             d = (meta->drift + d) * (1.0 + 1e-12);
             const int tail_max = min(GRID_TAIL_MAX, 32 + meta->n_built / 4);
@@ -736,8 +674,7 @@ __global__ __launch_bounds__(256) void diag_max_kernel(const T* __restrict__ P, 
         v = (double)P[p_off(ld, tlog, i, i)];
         if (!(v >= 0.0)) v = __builtin_inf();
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = fmax(v, __shfl_xor(v, off));
+    v = wave_max(v);
     if ((threadIdx.x & 63) == 0 && v > 0.0) atomicMax(pmax, (unsigned long long)__double_as_longlong(v));
 }
 
@@ -761,19 +698,12 @@ int ensure_pmax(slam_ekf* h) {
 }
 
 // ---- the grid form's host side ----
-static int grid_alloc_zero(void** p, size_t bytes, hipStream_t s) {
-    *p = nullptr;
-    HIP_TRY(hipMalloc(p, bytes));
-    HIP_TRY(hipMemsetAsync(*p, 0, bytes, s));
-    return SLAM_OK;
-}
-
 static int ensure_grid(slam_ekf* h) {
     if (h->grid_meta) return SLAM_OK;
     int rc;
-    if ((rc = grid_alloc_zero(&h->grid_meta, sizeof(GridMeta), h->stream))) return rc;
-    if ((rc = grid_alloc_zero((void**)&h->grid_cells, sizeof(int32_t) * (GRID_MAX_G * GRID_MAX_G + 1), h->stream))) return rc;
-    if ((rc = grid_alloc_zero(&h->grid_items, sizeof(GridItem) * (size_t)(h->maxN > 0 ? h->maxN : 1), h->stream))) return rc;
+    if ((rc = slam_alloc_zero(&h->grid_meta, sizeof(GridMeta), h->stream))) return rc;
+    if ((rc = slam_alloc_zero(&h->grid_cells, sizeof(int32_t) * (GRID_MAX_G * GRID_MAX_G + 1), h->stream))) return rc;
+    if ((rc = slam_alloc_zero(&h->grid_items, sizeof(GridItem) * (size_t)(h->maxN > 0 ? h->maxN : 1), h->stream))) return rc;
     h->grid_force = 1;
     h->grid_upd = 0;
     return SLAM_OK;

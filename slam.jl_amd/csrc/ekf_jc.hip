@@ -2,10 +2,10 @@
 // slam_ekf_joint_nis (include/slamhip_jc.h, which states the rule).  The companion library libslamhip_jc.so.
 //
 // Four launches on the handle's stream, no host round trip between them:
-//   1. jc_sweep_kernel   one thread per landmark, every observation: nis as the gating sweep forms it (pair_const / pair_eval below are
-//                        the functions of ekf_gate.hip, which keeps them in its anonymous namespace: restated here so that file stays
-//                        untouched).  A candidate (nis < gate1) is appended to its observation's list through an INTEGER counter; the
-//                        list holds N entries per observation, so it cannot overflow.  min_i: per-workgroup partial minima, no atomics.
+//   1. jc_sweep_kernel   one thread per landmark, every observation: nis as the gating sweep forms it (pair_const / pair_eval of
+//                        device_math.h, the functions ekf_gate.hip uses).  A candidate (nis < gate1) is appended to its observation's
+//                        list through an INTEGER counter; the list holds N entries per observation, so it cannot overflow.  min_i:
+//                        per-workgroup partial minima, no atomics.
 //   2. jc_lists_kernel   the small second launch, one workgroup: per observation the SLAM_JC_MAXCAND smallest (nis, j) in order (a
 //                        selection that does not depend on the order of arrival), min_i, rem, the table of distinct candidate
 //                        landmarks in order of first appearance and every candidate's index into it; the counters are re-armed.
@@ -76,56 +76,6 @@ struct slam_ekf_jc {
 
 namespace {
 
-// ---- the pair arithmetic of ekf_gate.hip, restated (see the head of this file) ---------------------------------------------------
-struct PairConst {
-    double zp0, zp1;
-    double qa, qb, qc;
-};
-
-__device__ inline PairConst pair_const(const ObsModel& om, const double* pvv, const double pfv[2][3], const double pff[4],
-                                       const double R[4]) {
-    PairConst pc;
-    pc.zp0 = om.zp[0];
-    pc.zp1 = om.zp[1];
-    double A[2][3], B[2][2], Cc[2][3], D[2][2];
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            A[r][c] = om.Hv[r * 3 + 0] * pvv[0 * 3 + c] + om.Hv[r * 3 + 1] * pvv[1 * 3 + c] + om.Hv[r * 3 + 2] * pvv[2 * 3 + c];
-            Cc[r][c] = om.Hf[r * 2 + 0] * pfv[0][c] + om.Hf[r * 2 + 1] * pfv[1][c];
-        }
-#pragma unroll
-        for (int a = 0; a < 2; ++a) {
-            B[r][a] = om.Hv[r * 3 + 0] * pfv[a][0] + om.Hv[r * 3 + 1] * pfv[a][1] + om.Hv[r * 3 + 2] * pfv[a][2];
-            D[r][a] = om.Hf[r * 2 + 0] * pff[0 * 2 + a] + om.Hf[r * 2 + 1] * pff[1 * 2 + a];
-        }
-    }
-    double S[2][2];
-#pragma unroll
-    for (int r = 0; r < 2; ++r)
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            double s = A[r][0] * om.Hv[q * 3 + 0] + A[r][1] * om.Hv[q * 3 + 1] + A[r][2] * om.Hv[q * 3 + 2];
-            s += B[r][0] * om.Hf[q * 2 + 0] + B[r][1] * om.Hf[q * 2 + 1];
-            s += Cc[r][0] * om.Hv[q * 3 + 0] + Cc[r][1] * om.Hv[q * 3 + 1] + Cc[r][2] * om.Hv[q * 3 + 2];
-            s += D[r][0] * om.Hf[q * 2 + 0] + D[r][1] * om.Hf[q * 2 + 1];
-            S[r][q] = s + R[q * 2 + r];
-        }
-    const double det = S[0][0] * S[1][1] - S[0][1] * S[1][0];
-    const double rdet = 1.0 / det;
-    pc.qa = S[1][1] * rdet;
-    pc.qb = -(S[0][1] + S[1][0]) * rdet;
-    pc.qc = S[0][0] * rdet;
-    return pc;
-}
-
-__device__ inline double pair_nis(const PairConst& pc, double z0, double z1) {
-    const double v0 = z0 - pc.zp0;
-    const double v1 = mpi_to_pi_d(z1 - pc.zp1);
-    return pc.qa * v0 * v0 + pc.qb * v0 * v1 + pc.qc * v1 * v1;
-}
-
 template <typename T>
 __device__ inline void load_pose(const T* __restrict__ x, const T* __restrict__ P, int ld, int L, double pose[3], double pvv[9]) {
     pose[0] = (double)x[0];
@@ -135,21 +85,6 @@ __device__ inline void load_pose(const T* __restrict__ x, const T* __restrict__ 
     for (int r = 0; r < 3; ++r)
 #pragma unroll
         for (int c = 0; c < 3; ++c) pvv[r * 3 + c] = (double)P[p_off(ld, L, r, c)];      // diagonal tile 0: stored complete
-}
-
-__device__ __forceinline__ double wave_min(double m) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const double o = __shfl_xor(m, off);
-        if (o < m) m = o;
-    }
-    return m;
-}
-
-__device__ __forceinline__ double wave_sum(double s) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off);       // (a + b == b + a: every lane ends with the same bits)
-    return s;
 }
 
 // the double of lane `src` (wave-uniform) in every lane: two v_readlane_b32
@@ -165,7 +100,7 @@ __global__ __launch_bounds__(JC_SWEEP) void jc_sweep_kernel(const T* __restrict_
                                                             double R0, double R1, double R2, double R3, double gate1,
                                                             double* __restrict__ list_nis, int32_t* __restrict__ list_j, int cap,
                                                             double* __restrict__ part, int nblk) {
-    constexpr int L = sizeof(T) == 4 ? 7 : 6;
+    constexpr int L = kTileLog2<T>;
     __shared__ double zs[2 * JC_OBS];
     __shared__ double wmin[JC_SWEEP / 64][JC_OBS];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -196,7 +131,8 @@ __global__ __launch_bounds__(JC_SWEEP) void jc_sweep_kernel(const T* __restrict_
     for (int i = 0; i < nz; ++i) {
         double m = INF;
         if (valid) {
-            const double nis = pair_nis(pc, zs[2 * i], zs[2 * i + 1]);
+            double nis, nd;                                                     // (nd: the gating sweep's, unused here)
+            pair_eval(pc, zs[2 * i], zs[2 * i + 1], nis, nd);
             if (nis < gate1) {                                                  // (false for a NaN)
                 const int e = atomicAdd(&w->cnt[i], 1);                         // e < N <= cap: one append per landmark at most
                 list_nis[(size_t)i * cap + e] = nis;
@@ -315,7 +251,7 @@ __global__ __launch_bounds__(256) void jc_lists_kernel(JcWork* __restrict__ w, i
 template <typename T>
 __global__ __launch_bounds__(64) void jc_cross_kernel(const T* __restrict__ x, const T* __restrict__ P, int ld, JcWork* __restrict__ w,
                                                       int Ufixed, double R0, double R1, double R2, double R3, double* __restrict__ M) {
-    constexpr int L = sizeof(T) == 4 ? 7 : 6;
+    constexpr int L = kTileLog2<T>;
     const int U = Ufixed >= 0 ? Ufixed : w->U;
     const int a = blockIdx.y, b = blockIdx.x * 64 + (int)threadIdx.x;
     if (a >= U || b > a) return;

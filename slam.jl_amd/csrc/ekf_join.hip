@@ -41,8 +41,6 @@
 
 namespace {
 
-__host__ __device__ inline int grp_first(int g) { return g < 2 ? 2 * g : 2 * g - 1; }
-
 constexpr int SC = 8;     // columns a strip wave walks
 constexpr int CG = 4;     // column groups a block workgroup walks
 
@@ -59,7 +57,7 @@ __global__ void join_trig_kernel(const T* __restrict__ xa, double* __restrict__ 
 template <typename T>
 __device__ __forceinline__ void join_strip(T* __restrict__ Pa, int lda, int nA, const double* __restrict__ cs, const T* __restrict__ xb,
                                            int NB, int bx, int by) {
-    constexpr int L = sizeof(T) == 4 ? 7 : 6;
+    constexpr int L = kTileLog2<T>;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int j = by * 64 + lane;
     if (j >= NB) return;
@@ -81,7 +79,7 @@ __device__ __forceinline__ void join_strip(T* __restrict__ Pa, int lda, int nA, 
 template <typename T>
 __device__ __forceinline__ void join_block(T* __restrict__ Pa, int lda, int NA, T* __restrict__ xa, const double* __restrict__ cs,
                                            const T* __restrict__ Pb, int ldb, const T* __restrict__ xb, int NB, int bx, int by) {
-    constexpr int L = sizeof(T) == 4 ? 7 : 6;
+    constexpr int L = kTileLog2<T>;
     const int gr = 2 + bx * 256 + (int)threadIdx.x;
     if (gr >= NB + 2) return;
     const int gc0 = by * CG;
@@ -140,7 +138,7 @@ __global__ __launch_bounds__(256) void join_rows_kernel(T* __restrict__ Pa, int 
 template <typename T>
 __global__ __launch_bounds__(256) void join_vehicle_kernel(T* __restrict__ Pa, int lda, int nA, const double* __restrict__ cs,
                                                             const T* __restrict__ xb) {
-    constexpr int L = sizeof(T) == 4 ? 7 : 6;
+    constexpr int L = kTileLog2<T>;
     const int col = 3 + blockIdx.x * 256 + (int)threadIdx.x;
     if (col >= nA) return;
     const double c = cs[0], s = cs[1];
@@ -157,7 +155,7 @@ __global__ __launch_bounds__(256) void join_vehicle_kernel(T* __restrict__ Pa, i
 template <typename T>
 __global__ void join_pose_kernel(T* __restrict__ Pa, int lda, T* __restrict__ xa, const double* __restrict__ cs,
                                  const T* __restrict__ Pb, int ldb, const T* __restrict__ xb) {
-    constexpr int L = sizeof(T) == 4 ? 7 : 6;
+    constexpr int L = kTileLog2<T>;
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
     const double phi = (double)xa[2];
     const double c = cs[0], s = cs[1];
@@ -225,31 +223,17 @@ extern "C" int slam_ekf_join(slam_ekf_t a, slam_ekf_t b, int32_t* first_new) {
     int rc;
     if (b->pending_status && (rc = slam_ekf_sync(b))) return rc;         // b's deferred status; a untouched
     HIP_TRY(hipSetDevice(a->device));
-    hipEvent_t eb = nullptr, ea = nullptr;
-    HIP_TRY(hipEventCreateWithFlags(&eb, hipEventDisableTiming));
-    hipError_t e = hipEventCreateWithFlags(&ea, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventRecord(eb, b->stream);
-    if (e == hipSuccess) e = hipStreamWaitEvent(a->stream, eb, 0);       // behind everything enqueued on b
-    rc = SLAM_OK;
-    if (e == hipSuccess) {
+    // (after a failed launch slam_between's events still run, so that b never overtakes what was enqueued; a launch that fails half
+    //  way leaves a's state undefined, as slamhip_join.h says)
+    return slam_between(a->stream, b->stream, [&]() -> int {
         const int NA = a->N;
-        rc = a->dtype == SLAM_F32 ? join_impl<float>(a, b) : join_impl<double>(a, b);
-        if (rc == SLAM_OK) {
-            // the launches have gone out: the host side follows the device at once, whatever the event calls below return
-            if (first_new) *first_new = NA + 1;
-            a->N = NA + b->N;
-            a->grid_force = 1;                                           // the grid belongs to the old means and the old count
-            a->pmax_valid = 0;                                           // new variances, and the vehicle's enter every one
-            rc = launch_side_rebuild(a);                                 // the packed 2 x 2 diagonal blocks follow the matrix
-        }
-        // (after a failed launch the events still run, so that b never overtakes what was enqueued; a launch that fails half way
-        //  leaves a's state undefined, as slamhip_join.h says)
-        e = hipEventRecord(ea, a->stream);                               // the last read of b lies before this
-        if (e == hipSuccess) e = hipStreamWaitEvent(b->stream, ea, 0);
-    }
-    (void)hipEventDestroy(eb);                                            // (released by the runtime once they have completed)
-    if (ea) (void)hipEventDestroy(ea);
-    if (rc) return rc;
-    HIP_TRY(e);
-    return SLAM_OK;
+        const int rcj = a->dtype == SLAM_F32 ? join_impl<float>(a, b) : join_impl<double>(a, b);
+        if (rcj) return rcj;
+        // the launches have gone out: the host side follows the device at once, whatever the event calls behind them return
+        if (first_new) *first_new = NA + 1;
+        a->N = NA + b->N;
+        a->grid_force = 1;                                               // the grid belongs to the old means and the old count
+        a->pmax_valid = 0;                                               // new variances, and the vehicle's enter every one
+        return launch_side_rebuild(a);                                   // the packed 2 x 2 diagonal blocks follow the matrix
+    });
 }

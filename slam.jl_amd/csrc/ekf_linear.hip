@@ -72,7 +72,7 @@ __global__ __launch_bounds__(256) void linear_factor_kernel(const T* __restrict_
                                                              const double* __restrict__ blob, int k, int mode, unsigned wrap,
                                                              double* __restrict__ Cout, double* __restrict__ gout,
                                                              double* __restrict__ out4, int32_t* __restrict__ status) {
-    constexpr int L = sizeof(T) == 4 ? 7 : 6;
+    constexpr int L = kTileLog2<T>;
     __shared__ double M[LK][LP], Li[LK][LP], v[LK], y[LK], sval[LNZ];
     __shared__ int sptr[LK + 1], sidx[LNZ];
     const int tid = threadIdx.x;
@@ -169,7 +169,7 @@ __global__ __launch_bounds__(PANEL_THREADS) void linear_panel_kernel(T* __restri
                                                             const double* __restrict__ blob, int k, const double* __restrict__ Cin,
                                                             const double* __restrict__ gin, T* __restrict__ W1, int pitchW,
                                                             const int32_t* __restrict__ status) {
-    constexpr int L = sizeof(T) == 4 ? 7 : 6;
+    constexpr int L = kTileLog2<T>;
     __shared__ double Cs[LK * LK], gs[LK], sval[LNZ];
     __shared__ int sptr[LK + 1], sidx[LNZ];
     const bool bad = status[0] != 0;                                      // (uniform)

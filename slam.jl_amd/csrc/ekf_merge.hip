@@ -36,7 +36,7 @@ __global__ __launch_bounds__(FD_TB) void find_dup_kernel(const T* __restrict__ x
                                                           const T* __restrict__ side, int side_n, int N, double gate,
                                                           int2* __restrict__ pairs, unsigned long long cap,
                                                           unsigned long long* __restrict__ cursor) {
-    constexpr int L = sizeof(T) == 4 ? 7 : 6;
+    constexpr int L = kTileLog2<T>;
     const int a0 = blockIdx.y * FD_TA, b0 = blockIdx.x * FD_TB;          // 0-based landmarks
     const int bend = b0 + FD_TB < N ? b0 + FD_TB : N;
     if (a0 >= bend - 1) return;                                          // no pair a < b in this block
@@ -130,7 +130,7 @@ template <typename T>
 __global__ __launch_bounds__(64) void merge_factor_kernel(const T* __restrict__ x, const T* __restrict__ P, int ld, MergeArgs A,
                                                            double* __restrict__ Cout, double* __restrict__ gout,
                                                            int32_t* __restrict__ status) {
-    constexpr int L = sizeof(T) == 4 ? 7 : 6;
+    constexpr int L = kTileLog2<T>;
     __shared__ double M[MK][MP], Li[MK][MP], v[MK], y[MK];
     __shared__ int fa[SLAM_MERGE_MAX], fb[SLAM_MERGE_MAX];
     const int tid = threadIdx.x, k = 2 * A.cnt;
@@ -214,7 +214,7 @@ template <typename T>
 __global__ __launch_bounds__(256) void merge_panel_kernel(T* __restrict__ x, const T* __restrict__ P, int ld, int n, MergeArgs A,
                                                            const double* __restrict__ Cin, const double* __restrict__ gin,
                                                            T* __restrict__ W1, int pitchW, const int32_t* __restrict__ status) {
-    constexpr int L = sizeof(T) == 4 ? 7 : 6;
+    constexpr int L = kTileLog2<T>;
     if (status[0] != 0) return;
     __shared__ double Cs[MK * MK], gs[MK];
     __shared__ int fa[SLAM_MERGE_MAX], fb[SLAM_MERGE_MAX];

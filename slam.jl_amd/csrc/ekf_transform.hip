@@ -37,9 +37,6 @@
 
 namespace {
 
-__host__ __device__ inline int grp_first(int g) { return g < 2 ? 2 * g : 2 * g - 1; }
-__host__ __device__ inline int grp_size(int g) { return g == 1 ? 1 : 2; }
-
 // the block (gr, gc), gr >= gc, entry by entry through p_off / p_store_sym
 template <typename T>
 __device__ __forceinline__ void transform_block(T* __restrict__ P, int ld, int L, int gr, int gc, double c, double s) {
@@ -81,7 +78,7 @@ constexpr int DIAG_SPLIT = 8;          // workgroups per diagonal tile (its ~200
 // h(gr) == h(gc) == D; workgroup b: part b % DIAG_SPLIT of diagonal tile b / DIAG_SPLIT
 template <typename T>
 __device__ __forceinline__ void transform_diag(T* __restrict__ P, int ld, int NG, double c, double s, int b) {
-    constexpr int L = sizeof(T) == 4 ? 7 : 6;
+    constexpr int L = kTileLog2<T>;
     int lo, hi;
     grp_range(b / DIAG_SPLIT, L, NG, &lo, &hi);
     const int K = hi - lo + 1;
@@ -95,7 +92,7 @@ __device__ __forceinline__ void transform_diag(T* __restrict__ P, int ld, int NG
 // row groups: every one with h(gr) > h(gc), 256 per workgroup (bx)
 template <typename T>
 __device__ __forceinline__ void transform_cols(T* __restrict__ P, int ld, int NG, double c, double s, int bx, int y) {
-    constexpr int L = sizeof(T) == 4 ? 7 : 6;
+    constexpr int L = kTileLog2<T>;
     constexpr int half = 1 << (L - 1);
     const int gc = y < 2 ? y : (y - 1) * half;
     const int D = y < 2 ? 0 : y - 2;
@@ -124,7 +121,7 @@ template <> struct Pair<double> { typedef double2 type; };
 template <typename T>
 __device__ __forceinline__ void transform_tile(T* __restrict__ P, int ld, int n, double c, double s, int I, int J) {
     typedef typename Pair<T>::type V;
-    constexpr int L = sizeof(T) == 4 ? 7 : 6;
+    constexpr int L = kTileLog2<T>;
     constexpr int E = 1 << L, LPC = E / 2, CPW = 64 / LPC;               // lanes per column pair, column pairs per wave
     if ((I << L) >= n) return;
     T* __restrict__ tile = P + tile_base(I, J, ld >> L, L);
@@ -203,7 +200,7 @@ __global__ __launch_bounds__(256) void transform_x_kernel(T* __restrict__ x, int
 
 template <typename T>
 int transform_impl(slam_ekf* h, double c, double s, double tx, double ty, double theta, bool rotate) {
-    constexpr int L = sizeof(T) == 4 ? 7 : 6;
+    constexpr int L = kTileLog2<T>;
     const int NG = h->N + 2, n = 3 + 2 * h->N;
     hipLaunchKernelGGL(transform_x_kernel<T>, dim3((NG + 255) / 256), dim3(256), 0, h->stream, (T*)h->x, NG, c, s, tx, ty, theta);
     HIP_TRY(hipGetLastError());

@@ -34,21 +34,9 @@ constexpr int HO_KC = 32;                  // particles per LDS chunk
 constexpr int HO_WSLAB = 4096;             // particles per workgroup of ho_weights_kernel
 constexpr uint32_t HO_STREAM = STREAM_HANDOVER;
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-
-template <typename T> struct Ho;
-template <> struct Ho<float> {
-    static constexpr int L = 7, MB = 32, KS = 2, NREG = 16, LSH = 5, SLAB = SLAM_HANDOVER_SLAB_F32;
-    typedef f32x16 Acc;
-    static __device__ __forceinline__ Acc mfma(float a, float b, Acc c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
-    static __device__ __forceinline__ int out_i(int reg, int half) { return (reg & 3) + 8 * (reg >> 2) + 4 * half; }     // index of the A dimension
-};
-template <> struct Ho<double> {
-    static constexpr int L = 6, MB = 16, KS = 4, NREG = 4, LSH = 4, SLAB = SLAM_HANDOVER_SLAB_F64;
-    typedef f64x4 Acc;
-    static __device__ __forceinline__ Acc mfma(double a, double b, Acc c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
-    static __device__ __forceinline__ int out_i(int reg, int half) { return 4 * reg + half; }
+// the MFMA tile (device_math.h) and SLAB: the particles of one partial
+template <typename T> struct Ho : MfmaTile<T> {
+    static constexpr int SLAB = sizeof(T) == 4 ? SLAM_HANDOVER_SLAB_F32 : SLAM_HANDOVER_SLAB_F64;
 };
 
 // ---- particles -> EKF ------------------------------------------------------------------------------------------------------
@@ -243,32 +231,9 @@ int ho_workspace(slam_pf* h, size_t bytes) {
     return SLAM_OK;
 }
 
-inline size_t ho_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
 int ho_check_pf(const slam_pf* pf) {
     ARG_CHECK(pf->n == pf->n_global && pf->d_peers == nullptr,
               "the hand-over supports only a filter that lives wholly on one shard, without peers");
-    return SLAM_OK;
-}
-
-// the two streams around the work on dst's stream (slam_ekf_join's order); `body` enqueues on sd
-template <typename F>
-int ho_between(hipStream_t sd, hipStream_t ss, F body) {
-    hipEvent_t es = nullptr, ed = nullptr;
-    HIP_TRY(hipEventCreateWithFlags(&es, hipEventDisableTiming));
-    hipError_t e = hipEventCreateWithFlags(&ed, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventRecord(es, ss);
-    if (e == hipSuccess) e = hipStreamWaitEvent(sd, es, 0);              // behind everything enqueued on src
-    int rc = SLAM_OK;
-    if (e == hipSuccess) {
-        rc = body();
-        e = hipEventRecord(ed, sd);                                      // the last read of src lies before this
-        if (e == hipSuccess) e = hipStreamWaitEvent(ss, ed, 0);
-    }
-    (void)hipEventDestroy(es);
-    if (ed) (void)hipEventDestroy(ed);
-    if (rc) return rc;
-    HIP_TRY(e);
     return SLAM_OK;
 }
 
@@ -292,9 +257,9 @@ int to_ekf_impl(slam_ekf* dst, slam_pf* src, const std::vector<int32_t>& slots, 
         host[3 + 2 * (size_t)i] = r[1] / W; host[4 + 2 * (size_t)i] = r[2] / W;
         for (int k = 0; k < 3; ++k) host[(size_t)nn + 3 * (size_t)i + k] = r[6 + k] / W;
     }
-    const size_t o_mu = 0, o_within = o_mu + ho_align(sizeof(double) * nn), o_w2 = o_within + ho_align(sizeof(double) * 3 * (cnt + 1)),
-                 o_slots = o_w2 + ho_align(sizeof(double) * nwb), o_sw = o_slots + ho_align(sizeof(int32_t) * (cnt + 1)),
-                 o_part = o_sw + ho_align(sizeof(T) * (size_t)n), total = o_part + sizeof(T) * ntiles * (size_t)nslabs * (size_t)(E * E);
+    const size_t o_mu = 0, o_within = o_mu + slam_align256(sizeof(double) * nn), o_w2 = o_within + slam_align256(sizeof(double) * 3 * (cnt + 1)),
+                 o_slots = o_w2 + slam_align256(sizeof(double) * nwb), o_sw = o_slots + slam_align256(sizeof(int32_t) * (cnt + 1)),
+                 o_part = o_sw + slam_align256(sizeof(T) * (size_t)n), total = o_part + sizeof(T) * ntiles * (size_t)nslabs * (size_t)(E * E);
     int rc;
     HIP_TRY(hipStreamSynchronize(src->stream));                          // (the scratch may be replaced)
     if ((rc = ho_workspace(src, total))) return rc;
@@ -308,7 +273,7 @@ int to_ekf_impl(slam_ekf* dst, slam_pf* src, const std::vector<int32_t>& slots, 
     std::vector<double> w2(nwb);
     const double pend = src->has_pending ? src->pending_shift : 0.0;     // read, not taken: src keeps its shift pending
     hipStream_t s = dst->stream;
-    rc = ho_between(s, src->stream, [&]() -> int {
+    rc = slam_between(s, src->stream, [&]() -> int {
         int rcb;
         if (cnt < dst->N && (rcb = ho_zero_panels(dst))) return rcb;
         HIP_TRY(hipMemcpyAsync(d_mu, host.data(), sizeof(double) * nn, hipMemcpyHostToDevice, s));
@@ -507,8 +472,8 @@ template <typename T>
 int to_pf_impl(slam_pf* dst, slam_ekf* src, const std::vector<int32_t>& ids) {
     const int cnt = (int)ids.size();
     const int64_t n = dst->n;
-    const size_t o_tab = 0, o_ids = ho_align(sizeof(double) * (HO_TAB_HEAD + (size_t)HO_TAB_ROW * (cnt + 1))),
-                 o_status = o_ids + ho_align(sizeof(int32_t) * (cnt + 1)), total = o_status + 256;
+    const size_t o_tab = 0, o_ids = slam_align256(sizeof(double) * (HO_TAB_HEAD + (size_t)HO_TAB_ROW * (cnt + 1))),
+                 o_status = o_ids + slam_align256(sizeof(int32_t) * (cnt + 1)), total = o_status + 256;
     int rc;
     HIP_TRY(hipStreamSynchronize(dst->stream));                          // (the scratch may be replaced)
     if ((rc = ho_workspace(dst, total))) return rc;
@@ -519,7 +484,7 @@ int to_pf_impl(slam_pf* dst, slam_ekf* src, const std::vector<int32_t>& ids) {
     hipStream_t s = dst->stream;
     int32_t status = 0;
     // the table, and its verdict, before anything of dst is written
-    rc = ho_between(s, src->stream, [&]() -> int {
+    rc = slam_between(s, src->stream, [&]() -> int {
         HIP_TRY(hipMemsetAsync(d_status, 0, sizeof(int32_t), s));
         if (cnt) HIP_TRY(hipMemcpyAsync(d_ids, ids.data(), sizeof(int32_t) * cnt, hipMemcpyHostToDevice, s));
         hipLaunchKernelGGL(ho_table_kernel<T>, dim3(1), dim3(256), 0, s, (const T*)src->x, (const T*)src->P, src->ld, (const int32_t*)d_ids, cnt,

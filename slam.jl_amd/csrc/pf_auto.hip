@@ -30,23 +30,6 @@ namespace {
 
 // (the step kernels' arguments, PfAutoArgs, and their common prologue, PfAutoStep: pf_device.h)
 
-// the first NS of six sums at once: one LDS exchange and one barrier pair for all of them (256 threads); the result reaches every thread
-template <int NS = 6>
-__device__ __forceinline__ void block_reduce6(double (&v)[6], double (*sh6)[6]) {
-#pragma unroll
-    for (int i = 0; i < NS; ++i)
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) v[i] += __shfl_xor(v[i], off);
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    __syncthreads();
-    if (lane == 0)
-#pragma unroll
-        for (int i = 0; i < NS; ++i) sh6[wave][i] = v[i];
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < NS; ++i) v[i] = sh6[0][i] + sh6[1][i] + sh6[2][i] + sh6[3][i];
-}
-
 
 // slam_pf_flush's request: the outcome of the LAST completed step, whatever its number.  (After a halt nothing is to be
 // said: the halting step has published itself and the steps behind it were skipped.)

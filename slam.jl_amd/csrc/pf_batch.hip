@@ -450,7 +450,7 @@ static bool pb_filter_ok(const slam_pf* h) {
 
 static int pb_ensure_buffers(slam_pf* h) {
     if (h->d_pb_lines) return SLAM_OK;
-    return pf_alloc(&h->d_pb_lines, sizeof(double) * 2 * PB_LINE_CAP * 8, h->stream);
+    return slam_alloc_zero(&h->d_pb_lines, sizeof(double) * 2 * PB_LINE_CAP * 8, h->stream);
 }
 
 // One persistent launch for kc steps that cannot resample; the steps are already in the host's log.

@@ -276,29 +276,6 @@ int pc_workspace(slam_pf* h, size_t bytes) {
     return SLAM_OK;
 }
 
-inline size_t pc_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
-// the two streams around the work on dst's stream (ho_between's order); `body` enqueues on sd
-template <typename F>
-int pc_between(hipStream_t sd, hipStream_t ss, F body) {
-    hipEvent_t es = nullptr, ed = nullptr;
-    HIP_TRY(hipEventCreateWithFlags(&es, hipEventDisableTiming));
-    hipError_t e = hipEventCreateWithFlags(&ed, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventRecord(es, ss);
-    if (e == hipSuccess) e = hipStreamWaitEvent(sd, es, 0);              // behind everything enqueued on src
-    int rc = SLAM_OK;
-    if (e == hipSuccess) {
-        rc = body();
-        e = hipEventRecord(ed, sd);                                      // the last read of src lies before this
-        if (e == hipSuccess) e = hipStreamWaitEvent(ss, ed, 0);
-    }
-    (void)hipEventDestroy(es);
-    if (ed) (void)hipEventDestroy(ed);
-    if (rc) return rc;
-    HIP_TRY(e);
-    return SLAM_OK;
-}
-
 int pc_check_pair(const slam_pf* dst, const slam_pf* src) {
     ARG_CHECK(dst != nullptr && src != nullptr, "null handle");
     ARG_CHECK(dst != src, "dst and src are the same handle");
@@ -344,9 +321,9 @@ int pc_move(slam_pf* dst, slam_pf* src, const std::vector<int32_t>& slots, int f
             work[k].meta = 0;
         }
     }
-    const size_t o_work = 0, o_anc = o_work + pc_align(sizeof(PcWork) * (size_t)dst->nl),
-                 o_cdf = o_anc + pc_align(resize ? sizeof(int32_t) * (size_t)m : 0), o_bsum = o_cdf + pc_align(resize ? sizeof(double) * (size_t)n : 0),
-                 total_bytes = o_bsum + pc_align(resize ? sizeof(double) * ((size_t)nb + 1) : 0);
+    const size_t o_work = 0, o_anc = o_work + slam_align256(sizeof(PcWork) * (size_t)dst->nl),
+                 o_cdf = o_anc + slam_align256(resize ? sizeof(int32_t) * (size_t)m : 0), o_bsum = o_cdf + slam_align256(resize ? sizeof(double) * (size_t)n : 0),
+                 total_bytes = o_bsum + slam_align256(resize ? sizeof(double) * ((size_t)nb + 1) : 0);
     int rc;
     HIP_TRY(hipStreamSynchronize(dst->stream));                          // (the scratch may be replaced)
     if ((rc = pc_workspace(dst, total_bytes))) return rc;
@@ -360,7 +337,7 @@ int pc_move(slam_pf* dst, slam_pf* src, const std::vector<int32_t>& slots, int f
     if (resize) {
         // the cdf and its total, read back before anything of dst is written
         double total = 0.0;
-        rc = pc_between(s, src->stream, [&]() -> int {
+        rc = slam_between(s, src->stream, [&]() -> int {
             hipLaunchKernelGGL(pc_scan1_kernel<T>, dim3(nb), dim3(SCAN_BLOCK), 0, s, (const T*)src->logw, n, gmax, d_cdf, d_bsum, (T)pend);
             HIP_TRY(hipGetLastError());
             hipLaunchKernelGGL(pc_scan2_kernel, dim3(1), dim3(256), 0, s, d_bsum, nb);
@@ -373,7 +350,7 @@ int pc_move(slam_pf* dst, slam_pf* src, const std::vector<int32_t>& slots, int f
         ARG_CHECK(std::isfinite(total) && total > 0.0, "the weights sum to zero or are not finite");
     }
     // from here on dst is written
-    rc = pc_between(s, src->stream, [&]() -> int {
+    rc = slam_between(s, src->stream, [&]() -> int {
         HIP_TRY(hipMemcpyAsync(d_work, work.data(), sizeof(PcWork) * work.size(), hipMemcpyHostToDevice, s));
         if (resize) {
             hipLaunchKernelGGL(pc_ancestor_kernel, dim3(grid_for(m)), dim3(256), 0, s, (const double*)d_cdf, (const double*)d_bsum, nb, n, m, u0, d_anc);

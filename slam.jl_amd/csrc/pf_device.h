@@ -4,6 +4,7 @@
 // plan, bookkeeping and prologue.
 #pragma once
 #include "pf_internal.h"
+#include "wave_reduce.h"
 
 // No FMA contraction in the particle path: the arithmetic is specified operation by operation (the oracle is NumPy, which
 // rounds every operation), and the fused step kernels must reproduce the separate kernels bit for bit whatever the compiler
@@ -161,39 +162,21 @@ __device__ __forceinline__ void fold_partials(const double* __restrict__ part, i
 // shift_b = m_b if `relative` else 0.
 // SC1 (auto mode): the partials are stored write-through at agent scope (global_store ... sc1) together with a tag, the
 // form in which another workgroup of the SAME launch may read them without an L2 write-back (part_key, pf_auto_tail).
-// six block sums at once: one LDS exchange and one barrier pair for all of them.  Same order of additions as six
-// block_reduce calls (xor tree inside the wave, then wave 0 + wave 1 + ...), so the sums are the same bit for bit.
-__device__ __forceinline__ void block_sum6(double (&v)[6], double (*sh6)[6]) {
+// the first NS of six block sums at once: one LDS exchange and one barrier pair for all of them; the result reaches every thread.
+// Same order of additions as NS block_reduce calls (xor tree inside the wave, then wave 0 + wave 1 + ...), so the sums are the
+// same bit for bit.
+template <int NS>
+__device__ __forceinline__ void block_sum(double (&v)[6], double (*sh6)[6]) {
 #pragma unroll
-    for (int i = 0; i < 6; ++i)
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) v[i] += __shfl_xor(v[i], off);
+    for (int i = 0; i < NS; ++i) v[i] = wave_sum(v[i]);
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     __syncthreads();
     if (lane == 0)
 #pragma unroll
-        for (int i = 0; i < 6; ++i) sh6[wave][i] = v[i];
+        for (int i = 0; i < NS; ++i) sh6[wave][i] = v[i];
     __syncthreads();
 #pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        double r = sh6[0][i];
-        for (int w = 1; w < (int)(blockDim.x >> 6); ++w) r += sh6[w][i];
-        v[i] = r;
-    }
-}
-
-// the first two of them only (same order of additions for those two: the same sums bit for bit)
-__device__ __forceinline__ void block_sum2(double (&v)[6], double (*sh6)[6]) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) v[i] += __shfl_xor(v[i], off);
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    __syncthreads();
-    if (lane == 0) { sh6[wave][0] = v[0]; sh6[wave][1] = v[1]; }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
+    for (int i = 0; i < NS; ++i) {
         double r = sh6[0][i];
         for (int w = 1; w < (int)(blockDim.x >> 6); ++w) r += sh6[w][i];
         v[i] = r;
@@ -240,9 +223,9 @@ __device__ __forceinline__ void block_weight_stats(T lw, T x, T y, T phi, bool v
     double v[6] = {e, e * e, 0.0, 0.0, 0.0, 0.0};
     if constexpr (POSE) {
         v[2] = e * (double)x; v[3] = e * (double)y; v[4] = e * sn; v[5] = e * cs;
-        block_sum6(v, sh6);
+        block_sum<6>(v, sh6);
     } else {
-        block_sum2(v, sh6);
+        block_sum<2>(v, sh6);
     }
     if (threadIdx.x == 0) {
         double* o = part + (size_t)blockIdx.x * 8;
@@ -303,9 +286,7 @@ __device__ __forceinline__ WRec wrec_combine4(const WRec& a, const WRec& b, cons
 template <typename T>
 __device__ __forceinline__ WRec wrec_wave(T lw, bool valid) {
     const double NEG = -__builtin_inf();
-    double m = valid ? (double)lw : NEG;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) m = fmax(m, __shfl_xor(m, off));
+    const double m = wave_max(valid ? (double)lw : NEG);
     WRec r;
     r.m = m;
     const bool live = valid && (double)lw > NEG && m > NEG;

@@ -236,14 +236,6 @@ constexpr int PF_PAR_MAX_N = 49152;          // one-box sweep (tools/gpu_r3m.sh)
         }                              \
     } while (0)
 
-template <typename P>
-inline int pf_alloc(P** p, size_t bytes, hipStream_t s) {
-    *p = nullptr;
-    if (bytes == 0) bytes = 16;
-    HIP_TRY(hipMalloc((void**)p, bytes));
-    HIP_TRY(hipMemsetAsync(*p, 0, bytes, s));
-    return SLAM_OK;
-}
 inline int grid_for(int64_t n) { return (int)((n + 255) / 256); }
 inline bool pf_sharded(const slam_pf* h) { return h->d_peers != nullptr && h->xchg_world > 1; }
 

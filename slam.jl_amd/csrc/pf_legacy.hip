@@ -538,18 +538,18 @@ static int pf_create_impl(slam_pf* h) {
         h->lm_chunk_bytes = per_lm << shift;
     }
     for (int b = 0; b < 2; ++b) {
-        if ((rc = pf_alloc(&h->pose[b], h->esz * 3 * n, h->stream))) return rc;
+        if ((rc = slam_alloc_zero(&h->pose[b], h->esz * 3 * n, h->stream))) return rc;
         for (int k = 0; k < h->lmtab.nchunks; ++k) {
             // (the last chunk holds what is left of the nl landmarks)
             const size_t lms = (size_t)h->nl - ((size_t)k << h->lmtab.shift) < ((size_t)1 << h->lmtab.shift)
                                    ? (size_t)h->nl - ((size_t)k << h->lmtab.shift) : ((size_t)1 << h->lmtab.shift);
-            if ((rc = pf_alloc(&h->lmtab.c[b][k], h->esz * 5 * n * lms, h->stream))) return rc;
+            if ((rc = slam_alloc_zero(&h->lmtab.c[b][k], h->esz * 5 * n * lms, h->stream))) return rc;
         }
     }
     HIP_TRY(hipMalloc((void**)&h->d_lmtab, sizeof(PfLmTab)));
     HIP_TRY(hipMemcpy(h->d_lmtab, &h->lmtab, sizeof(PfLmTab), hipMemcpyHostToDevice));
     for (int b = 0; b < 2; ++b)
-        if ((rc = pf_alloc(&h->logw2[b], h->esz * n, h->stream))) return rc;
+        if ((rc = slam_alloc_zero(&h->logw2[b], h->esz * n, h->stream))) return rc;
     h->lwcur = 0;
     h->logw = h->logw2[0];
     // the inbox the peers of a sharded filter write into: fine-grained device memory (polled while a peer GPU writes it)
@@ -564,19 +564,19 @@ static int pf_create_impl(slam_pf* h) {
     h->ocap = PF_OCAP;
     h->red_blocks = grid_for(h->n);                  // one partial record per 256 particles
     // (room for one statistics line per 64 particles: the observation-parallel step kernel's workgroups)
-    if ((rc = pf_alloc(&h->d_part, sizeof(double) * 8 * (size_t)((h->n + 63) / 64), h->stream))) return rc;
-    if ((rc = pf_alloc(&h->d_out, sizeof(double) * 8, h->stream))) return rc;
-    if ((rc = pf_alloc(&h->d_cdf, sizeof(double) * (size_t)h->n_global, h->stream))) return rc;
+    if ((rc = slam_alloc_zero(&h->d_part, sizeof(double) * 8 * (size_t)((h->n + 63) / 64), h->stream))) return rc;
+    if ((rc = slam_alloc_zero(&h->d_out, sizeof(double) * 8, h->stream))) return rc;
+    if ((rc = slam_alloc_zero(&h->d_cdf, sizeof(double) * (size_t)h->n_global, h->stream))) return rc;
     const size_t nb = ((size_t)h->n_global + SCAN_BLOCK - 1) / SCAN_BLOCK;
-    if ((rc = pf_alloc(&h->d_bsum, sizeof(double) * (nb + 1), h->stream))) return rc;
-    if ((rc = pf_alloc(&h->d_boff, sizeof(double) * (nb + 2), h->stream))) return rc;
-    if ((rc = pf_alloc(&h->d_src, sizeof(int32_t) * n, h->stream))) return rc;
-    if ((rc = pf_alloc(&h->d_anc, sizeof(int32_t) * n, h->stream))) return rc;
+    if ((rc = slam_alloc_zero(&h->d_bsum, sizeof(double) * (nb + 1), h->stream))) return rc;
+    if ((rc = slam_alloc_zero(&h->d_boff, sizeof(double) * (nb + 2), h->stream))) return rc;
+    if ((rc = slam_alloc_zero(&h->d_src, sizeof(int32_t) * n, h->stream))) return rc;
+    if ((rc = slam_alloc_zero(&h->d_anc, sizeof(int32_t) * n, h->stream))) return rc;
     HIP_TRY(hipHostMalloc((void**)&h->h_ids, sizeof(int32_t) * 4 * PF_OCAP, hipHostMallocDefault));
     memset(h->h_ids, 0, sizeof(int32_t) * 4 * PF_OCAP);
     for (int b = 0; b < 2; ++b)
-        if ((rc = pf_alloc(&h->d_tab[b], sizeof(int32_t) * (size_t)PF_TAB_MAX * n, h->stream))) return rc;
-    if ((rc = pf_alloc(&h->d_lmeta, sizeof(int32_t) * (size_t)h->nl, h->stream))) return rc;
+        if ((rc = slam_alloc_zero(&h->d_tab[b], sizeof(int32_t) * (size_t)PF_TAB_MAX * n, h->stream))) return rc;
+    if ((rc = slam_alloc_zero(&h->d_lmeta, sizeof(int32_t) * (size_t)h->nl, h->stream))) return rc;
     HIP_TRY(hipHostMalloc((void**)&h->h_obs, sizeof(double) * 4 * h->ocap, hipHostMallocDefault));
     for (int b = 0; b < 2; ++b) HIP_TRY(hipEventCreateWithFlags(&h->stage_ev[b], hipEventDisableTiming | hipEventDisableSystemFence));
     HIP_TRY(hipHostGetDevicePointer((void**)&h->h_ids_dev, h->h_ids, 0));
@@ -587,8 +587,8 @@ static int pf_create_impl(slam_pf* h) {
     h->out_seq = 0;
     h->pending_shift = 0.0; h->has_pending = 0;
     // auto mode
-    if ((rc = pf_alloc(&h->d_ctl, sizeof(PfCtl), h->stream))) return rc;
-    if ((rc = pf_alloc(&h->d_lmstate, sizeof(int32_t) * (size_t)h->nl, h->stream))) return rc;
+    if ((rc = slam_alloc_zero(&h->d_ctl, sizeof(PfCtl), h->stream))) return rc;
+    if ((rc = slam_alloc_zero(&h->d_lmstate, sizeof(int32_t) * (size_t)h->nl, h->stream))) return rc;
     HIP_TRY(hipHostMalloc((void**)&h->h_mir, sizeof(PfMirror), hipHostMallocDefault));
     memset(h->h_mir, 0, sizeof(PfMirror));
     HIP_TRY(hipHostGetDevicePointer((void**)&h->h_mir_dev, h->h_mir, 0));

@@ -26,7 +26,7 @@ The bound (derived, not measured)
     c is a condition, not a knob: the CPU emulation in tests/test_strip_ref_cpu.py needs c = 2.1 for the fp64 strip, and
     an emulated kernel whose strip arithmetic is `float` leaves the bound on 39-49 % of the entries even with c = 64.
 
-Storage (device_math.h:42-93)
+Storage (device_math.h:106-173)
     Tile-major, block lower: tiles of edge E (128 fp32, 64 fp64) on and below the diagonal, each one contiguous E x E
     column-major block, column band after column band.  `p_off` / `tile_base` are restated here on NumPy integers;
     `expected_storage` lays a dense matrix out that way; `check_storage` reads a live handle's raw buffer and asserts
@@ -182,7 +182,7 @@ def tile_base(I, J, T, L):
 
 
 def p_off(ld, L, r, c):
-    """device_math.h:56-59 on NumPy integers; requires (r >> L) >= (c >> L)."""
+    """device_math.h:136-139 on NumPy integers; requires (r >> L) >= (c >> L)."""
     r, c = np.asarray(r, dtype=np.int64), np.asarray(c, dtype=np.int64)
     m = (1 << L) - 1
     return tile_base(r >> L, c >> L, ld >> L, L) + ((c & m) << L) + (r & m)

@@ -151,7 +151,7 @@ def test_the_bound_admits_fp64_arithmetic_and_rejects_float_arithmetic(dtype):
 # ---- storage ------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("E", [64, 128])
 def test_p_off_against_a_direct_enumeration_of_the_tiles(E):
-    """device_math.h:42-59: band after band, inside a band tile I = J, J + 1, ..., each tile E x E column-major."""
+    """device_math.h:106-139: band after band, inside a band tile I = J, J + 1, ..., each tile E x E column-major."""
     L = E.bit_length() - 1
     T = 3
     ld = T * E

@@ -359,7 +359,7 @@ def _solve_upper(U, B):
 
 
 def front(x, P, z, Rm, ids, ft, wrap=True, hf_bearing_power=2, magnitude=False):
-    """Innovation v, A = P H', S = H A + RR symmetrised (oracle/ekf_ref.py: obs_blocks, _update_front; device_math.h:26-40),
+    """Innovation v, A = P H', S = H A + RR symmetrised (oracle/ekf_ref.py: obs_blocks, _update_front; device_math.h:28-42),
     evaluated in the float type `ft`.  `wrap` / `hf_bearing_power` exist for the planted defects; `magnitude` returns |P| |H'| in
     A's place (every product of P H' by its absolute value) and |z| + |zp| in v's."""
     x = np.asarray(x, dtype=ft)
