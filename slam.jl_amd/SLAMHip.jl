@@ -21,7 +21,8 @@ export SlamState, EKFSlamState, set_state!, predict, update, add_features, assoc
        upload!, resize, pose_bins, kld_particle_count, pf_meta, set_rng!,
        CovFactor, factor, factor!, logdet, isposdef, whiten, nees, sample,
        update_linear!, linear_nis, predict_linear!, predict_odometry!, fix_position!, fix_heading!, fix_landmark!,
-       step_proposal_unknown!, associate_proposal, proposal_max_obs
+       step_proposal_unknown!, associate_proposal, proposal_max_obs,
+       LocalArea, open_area!, close!, abort!, landmarks_within, accumulators, area_info, global_ids, local_state
 
 const libslamhip = get(ENV, "SLAMHIP_LIB", joinpath(@__DIR__, "libslamhip.so"))
 # the companion library of include/slamhip_frame.h (the rigid frame change); it links against libslamhip.so and lies beside it
@@ -58,6 +59,9 @@ const libslamhip_linear = get(ENV, "SLAMHIP_LINEAR_LIB", joinpath(@__DIR__, "lib
 # the extension library of include/ext/slamhip_proposal.h (FastSLAM 2.0 with unknown correspondences), same arrangement (opened at
 # the first step_proposal_unknown! / associate_proposal / proposal_max_obs)
 const libslamhip_proposal = get(ENV, "SLAMHIP_PROPOSAL_LIB", joinpath(@__DIR__, "libslamhip_proposal.so"))
+# the extension library of include/ext/slamhip_local.h (compressed local-area updates for the EKF), same arrangement (opened at the
+# first LocalArea; it also needs libslamhip_copy.so beside it)
+const libslamhip_local = get(ENV, "SLAMHIP_LOCAL_LIB", joinpath(@__DIR__, "libslamhip_local.so"))
 
 const SLAM_OK = Cint(0)
 const SLAM_PF_HALTED = Cint(1)
@@ -644,6 +648,130 @@ fix_position!(s::EKFSlamState, xy, R) = update_linear!(s, unit_rows(length(s), (
 fix_heading!(s::EKFSlamState, phi, var) = update_linear!(s, unit_rows(length(s), (3,)), [phi], fill(Float64(var), 1, 1); wrap = (1,))
 "    fix_landmark!(s, j, xy, R): landmark j was surveyed at xy with covariance R."
 fix_landmark!(s::EKFSlamState, j::Integer, xy, R) = update_linear!(s, unit_rows(length(s), (2 + 2j, 3 + 2j)), xy, R)
+
+# ---- compressed local-area updates (include/ext/slamhip_local.h) -----------------------------------------------------------------
+"""
+    LocalArea(s, ids; max_local = min(1024, length(ids) + 64))
+
+The compressed EKF over the vehicle and the landmarks `ids` of `s` (local landmark j is ids[j]; landmarks added in the area
+follow): `ekf_predict!`, `ekf_update!` (local ids, Cholesky form), `augment!`, `associate` and `observe!` work on a small state,
+`close!` brings `s` up to date in one pass (up to rounding the full filter's result), `abort!` discards the area.  While the area
+is open `s` must not be written.  `open_area!(a, ids)` opens the next area on the same object.
+"""
+mutable struct LocalArea{T<:Union{Float32,Float64}}
+    handle::Ptr{Cvoid}
+    parent::EKFSlamState{T}
+    state::Ptr{Cvoid}                             # the local EKF handle, owned by the library
+    ids::Vector{Int32}
+    function LocalArea(s::EKFSlamState{T}, ids::AbstractVector{<:Integer} = Int32[];
+                       max_local::Integer = min(1024, max(1, length(ids) + 64)), open::Bool = true) where {T}
+        h = Ref{Ptr{Cvoid}}(C_NULL)
+        check(ccall((:slam_ekf_local_create, libslamhip_local), Cint, (Ref{Ptr{Cvoid}}, Ptr{Cvoid}, Cint), h, handle(s), max_local))
+        l = Ref{Ptr{Cvoid}}(C_NULL)
+        check(ccall((:slam_ekf_local_state, libslamhip_local), Cint, (Ptr{Cvoid}, Ref{Ptr{Cvoid}}), h[], l))
+        a = new{T}(h[], s, l[], Int32[])
+        finalizer(a) do ar
+            ccall((:slam_ekf_local_destroy, libslamhip_local), Cint, (Ptr{Cvoid},), ar.handle)
+        end
+        open && open_area!(a, ids)
+        return a
+    end
+end
+
+function open_area!(a::LocalArea, ids::AbstractVector{<:Integer})
+    sel = collect(Int32, ids)
+    check(ccall((:slam_ekf_local_open, libslamhip_local), Cint, (Ptr{Cvoid}, Ptr{Int32}, Cint), a.handle, sel, length(sel)))
+    a.ids = sel
+    a
+end
+
+"    close!(a) -> first_new: the global state is brought up to date; the landmarks added in the area are first_new, first_new + 1, ..."
+function close!(a::LocalArea)
+    first = Ref{Cint}(0)
+    check(ccall((:slam_ekf_local_close, libslamhip_local), Cint, (Ptr{Cvoid}, Ref{Cint}), a.handle, first))
+    Int(first[])
+end
+
+"    abort!(a): discard the area; the global state is untouched."
+abort!(a::LocalArea) = (check(ccall((:slam_ekf_local_abort, libslamhip_local), Cint, (Ptr{Cvoid},), a.handle)); nothing)
+
+"    area_info(a) -> (open, n0, n_a, added, steps, N_open, max_local)"
+function area_info(a::LocalArea)
+    out = zeros(Int64, 8)
+    check(ccall((:slam_ekf_local_info, libslamhip_local), Cint, (Ptr{Cvoid}, Ptr{Int64}), a.handle, out))
+    (open = out[1] != 0, n0 = Int(out[2]), n_a = Int(out[3]), added = Int(out[4]), steps = Int(out[5]), N_open = Int(out[6]),
+     max_local = Int(out[7]))
+end
+
+"    global_ids(a): the global id of every local landmark, in local order."
+function global_ids(a::LocalArea)
+    i = area_info(a)
+    vcat(a.ids, Int32.(i.N_open .+ (1:i.added)))
+end
+
+"    accumulators(a) -> (phi n_a x n0, psi n0 x n0, theta n0), Float64 (the library returns row-major: transposed here)."
+function accumulators(a::LocalArea)
+    i = area_info(a)
+    phi = Matrix{Float64}(undef, i.n0, i.n_a); psi = Matrix{Float64}(undef, i.n0, i.n0); theta = Vector{Float64}(undef, i.n0)
+    check(ccall((:slam_ekf_local_get, libslamhip_local), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                a.handle, phi, psi, theta))
+    permutedims(phi), permutedims(psi), theta
+end
+
+"    local_state(a) -> (x, P) of the local state."
+function local_state(a::LocalArea{T}) where {T}
+    n = area_info(a).n_a
+    x = Vector{T}(undef, n); P = Matrix{T}(undef, n, n)
+    check(ccall((:slam_ekf_get_state, libslamhip), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cint), a.state, x, P, n, n))
+    x, P
+end
+
+function ekf_predict!(a::LocalArea, v::Real, g::Real, wheelbase::Real, Q::AbstractMatrix, dt::Real)
+    check(ccall((:slam_ekf_local_predict, libslamhip_local), Cint, (Ptr{Cvoid}, Cdouble, Cdouble, Cdouble, Ptr{Cdouble}, Cdouble),
+                a.handle, v, g, wheelbase, colmajor4(Q), dt))
+    nothing
+end
+
+function ekf_update!(a::LocalArea, z::AbstractMatrix, R::AbstractMatrix, idf; form::Symbol = :cholesky)
+    ids = collect(Int32, vec(collect(idf)))
+    check(ccall((:slam_ekf_local_update, libslamhip_local), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Int32}, Cint, Ptr{Cdouble}, Cint),
+                a.handle, pairs64(z), ids, length(ids), colmajor4(R), form === :joseph ? FORM_JOSEPH : FORM_CHOLESKY))
+    nothing
+end
+
+function augment!(a::LocalArea, z::AbstractMatrix, R::AbstractMatrix)
+    size(z, 2) == 0 && return nothing
+    check(ccall((:slam_ekf_local_augment, libslamhip_local), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Cint, Ptr{Cdouble}),
+                a.handle, pairs64(z), size(z, 2), colmajor4(R)))
+    nothing
+end
+
+"associate(a, z, R, gate1, gate2) -> (zf, idf, zn) against the LOCAL map: idf are local ids."
+function associate(a::LocalArea, z::AbstractMatrix, R::AbstractMatrix, gate1::Real, gate2::Real)
+    nz = size(z, 2)
+    assoc = zeros(Int32, nz)
+    if nz > 0
+        check(ccall((:slam_ekf_associate, libslamhip), Cint,
+                    (Ptr{Cvoid}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cdouble, Cdouble, Ptr{Int32}),
+                    a.state, pairs64(z), nz, colmajor4(R), gate1, gate2, assoc))
+    end
+    hit = findall(>(0), assoc)
+    z[:, hit], reshape(Int.(assoc[hit]), 1, :), z[:, findall(<(0), assoc)]
+end
+
+"observe!(a, z, R, gate1, gate2): associate on the local state, then update, then augment; returns (zf, idf, zn)."
+function observe!(a::LocalArea, z::AbstractMatrix, R::AbstractMatrix, gate1::Real, gate2::Real)
+    zf, idf, zn = associate(a, z, R, gate1, gate2)
+    size(zf, 2) > 0 && ekf_update!(a, zf, R, idf)
+    augment!(a, zn, R)
+    zf, idf, zn
+end
+
+"    landmarks_within(s, cx, cy, r): the ids of the landmarks whose mean lies within r of (cx, cy), from the downloaded mean."
+function landmarks_within(s::EKFSlamState, cx::Real, cy::Real, r::Real)
+    x = download(s, :x)
+    Int32[j for j in 1:nlandmarks(s) if hypot(x[2 + 2j] - cx, x[3 + 2j] - cy) <= r]
+end
 
 "feature_ellipses(x, cov) of the browser monitor (sim/browser/wsserver.jl:72-85): 5 x N [cx; cy; rx; ry; phi], on the device."
 function feature_ellipses(s::EKFSlamState)

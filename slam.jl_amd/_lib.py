@@ -372,6 +372,29 @@ proposal_lib = Companion("proposal", PROPOSAL_SIGNATURES)
 PROPOSAL_LIB_PATH = proposal_lib.path
 
 
+# ---- local: compressed local-area updates for the EKF, opened when the first area object is made ----------------------------------
+# Wired like linear, and like it entered in neither table; its surface checks are made by tests/test_local_ref_cpu.py.
+SLAM_LOCAL_MAXLM = 1024
+
+#: every symbol include/ext/slamhip_local.h declares
+LOCAL_SIGNATURES = {
+    "slam_ekf_local_create": (C.c_int, [C.POINTER(_h), _h, C.c_int]),
+    "slam_ekf_local_destroy": (C.c_int, [_h]),
+    "slam_ekf_local_open": (C.c_int, [_h, _ip, C.c_int]),
+    "slam_ekf_local_state": (C.c_int, [_h, C.POINTER(_h)]),
+    "slam_ekf_local_predict": (C.c_int, [_h, C.c_double, C.c_double, C.c_double, _dp, C.c_double]),
+    "slam_ekf_local_update": (C.c_int, [_h, _dp, _ip, C.c_int, _dp, C.c_int]),
+    "slam_ekf_local_augment": (C.c_int, [_h, _dp, C.c_int, _dp]),
+    "slam_ekf_local_close": (C.c_int, [_h, C.POINTER(C.c_int)]),
+    "slam_ekf_local_abort": (C.c_int, [_h]),
+    "slam_ekf_local_info": (C.c_int, [_h, _i64p]),
+    "slam_ekf_local_get": (C.c_int, [_h, _dp, _dp, _dp]),
+}
+
+local_lib = Companion("local", LOCAL_SIGNATURES)
+LOCAL_LIB_PATH = local_lib.path
+
+
 def proposal_max_obs() -> int:
     """Observations per call of the proposal step with unknown correspondences, as the library reports it."""
     out = (C.c_int * 4)()

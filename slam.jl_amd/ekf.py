@@ -37,7 +37,7 @@ __all__ = [
     "find_duplicates", "merge_features", "merge_features_", "merge_in_batches",
     "chi2_table", "associate_joint", "observe_joint",
     "copy_state", "select_features", "select_map", "grown_capacity",
-    "CovarianceFactor", "linear_rows",
+    "CovarianceFactor", "linear_rows", "LocalArea",
 ]
 
 _DTYPES = {"f32": (SLAM_F32, np.float32), "f64": (SLAM_F64, np.float64),
@@ -336,6 +336,9 @@ class EKFSlamState(SlamState):
         if getattr(self, "_jc", None):
             _lib.jc_lib().slam_ekf_jc_destroy(self._jc)               # the search workspace borrows the handle: it goes first
             self._jc = None
+        if getattr(self, "_borrowed", False):                            # the local handle of a LocalArea: its library owns it
+            self._h = C.c_void_p()
+            return
         if getattr(self, "_h", None) is not None and self._h:
             lib.slam_ekf_destroy(self._h)
             self._h = C.c_void_p()
@@ -864,6 +867,20 @@ class EKFSlamState(SlamState):
             check(rc)
         return assoc
 
+    # -- compressed local-area updates (include/ext/slamhip_local.h) ---------------------------
+    def landmarks_within(self, cx, cy, r):
+        """The ids (1-based, ascending, int32) of the landmarks whose mean lies within ``r`` of (cx, cy): a host choice from the
+        downloaded mean."""
+        x = np.asarray(self.download("x"), dtype=np.float64)
+        lm = x[3:].reshape(-1, 2)
+        near = np.hypot(lm[:, 0] - float(cx), lm[:, 1] - float(cy)) <= float(r)
+        return (np.flatnonzero(near) + 1).astype(np.int32)
+
+    def local(self, ids, max_local=None):
+        """A :class:`LocalArea` over the vehicle and the landmarks ``ids`` of this state, opened: a context manager that closes
+        the area on a clean exit and aborts it on an exception.  While it is open this state must not be written."""
+        return LocalArea(self, ids, max_local=max_local)
+
     # -- joint-compatibility data association (include/slamhip_jc.h) ---------------------------
     def _jc_handle(self):
         """The search workspace (slam_ekf_jc_create), made at the first joint call and destroyed by close()."""
@@ -1113,6 +1130,145 @@ class CovarianceFactor:
         count)) from the caller's ``numpy.random.Generator``, so the draw is the caller's to reproduce."""
         Z = rng.standard_normal((self.n, int(count)))
         return self.mean()[:, None] + self.colour(Z)
+
+
+class LocalArea:
+    """The compressed EKF over a local area (include/ext/slamhip_local.h): predict, update and add_features run on a small state
+    -- the vehicle plus the landmarks ``ids`` of ``state`` (local landmark j is ids[j - 1]; landmarks added here follow) -- and
+    :meth:`close` brings the rest of the map up to date in one pass.  Up to rounding the result is the full filter's.  While the
+    area is open ``state`` must not be written, and observations of landmarks outside the area cannot be used.  ``max_local``: the
+    local landmark capacity (default len(ids) + 64, at most 1024).  ``area.state`` is the local state as an EKFSlamState whose
+    handle this object owns: read it freely (download, associate, ellipses), write it only through this object."""
+
+    def __init__(self, state, ids=None, max_local=None):
+        if not isinstance(state, EKFSlamState):
+            raise TypeError("LocalArea needs an EKFSlamState")
+        self._lib = _lib.local_lib()
+        self.parent = state
+        self._L = C.c_void_p()
+        ids_arr = np.zeros(0, dtype=np.int32) if ids is None else np.asarray(ids, dtype=np.int32).reshape(-1)
+        if max_local is None:
+            max_local = min(_lib.SLAM_LOCAL_MAXLM, max(1, ids_arr.size + 64))
+        self.max_local = int(max_local)
+        check(self._lib.slam_ekf_local_create(C.byref(self._L), state._h, self.max_local))
+        h = C.c_void_p()
+        check(self._lib.slam_ekf_local_state(self._L, C.byref(h)))
+        st = EKFSlamState.__new__(EKFSlamState)
+        st.grow = False
+        st._gate_mode = None
+        st._async = None
+        st.np_dtype = state.np_dtype
+        st.max_landmarks = self.max_local
+        st.device = state.device
+        st._h = h
+        st._borrowed = True
+        self.state = st
+        if ids is not None:
+            try:
+                self.open(ids_arr)
+            except Exception:
+                self.destroy()
+                raise
+
+    # -- lifetime ----------------------------------------------------------------
+    def destroy(self):
+        """Release the local handle and the accumulators; an open area is discarded."""
+        if getattr(self, "state", None) is not None:
+            self.state.close()
+        if getattr(self, "_L", None) is not None and self._L:
+            self._lib.slam_ekf_local_destroy(self._L)
+            self._L = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        if self.is_open:
+            if exc_type is None:
+                self.close()
+            else:
+                self.abort()
+        return False
+
+    # -- the area ------------------------------------------------------------------
+    def open(self, ids):
+        ids = np.ascontiguousarray(np.asarray(ids, dtype=np.int32).reshape(-1))
+        check(self._lib.slam_ekf_local_open(self._L, _ptr(ids, C.c_int32) if ids.size else None, int(ids.size)))
+        self.ids = ids.copy()
+
+    def info(self):
+        out = (C.c_int64 * 8)()
+        check(self._lib.slam_ekf_local_info(self._L, out))
+        keys = ("open", "n0", "n_a", "added", "steps", "N_open", "max_local")
+        return {k: int(out[i]) for i, k in enumerate(keys)}
+
+    @property
+    def is_open(self):
+        return bool(self._L) and bool(self.info()["open"])
+
+    def global_ids(self):
+        """Global id of every local landmark, in local order: ``ids``, then the landmarks added here (N at open + 1 ...)."""
+        i = self.info()
+        return np.concatenate([self.ids, i["N_open"] + 1 + np.arange(i["added"], dtype=np.int32)]).astype(np.int32)
+
+    def accumulators(self):
+        """(phi n_a x n0, psi n0 x n0, theta n0) as float64 arrays (slam_ekf_local_get): for tests and diagnostics."""
+        i = self.info()
+        phi = np.zeros((i["n_a"], i["n0"]))
+        psi = np.zeros((i["n0"], i["n0"]))
+        theta = np.zeros(i["n0"])
+        check(self._lib.slam_ekf_local_get(self._L, _ptr(phi), _ptr(psi), _ptr(theta)))
+        return phi, psi, theta
+
+    def close(self):
+        """Bring the global state up to date (slam_ekf_local_close); returns the global id of the first landmark appended."""
+        first = C.c_int()
+        check(self._lib.slam_ekf_local_close(self._L, C.byref(first)))
+        return first.value
+
+    def abort(self):
+        """Discard the area: the global state is untouched."""
+        check(self._lib.slam_ekf_local_abort(self._L))
+
+    # -- the steps, on the local state ----------------------------------------------
+    def predict(self, v, g, wheelbase, Q, dt):
+        q = _small(Q)
+        check(self._lib.slam_ekf_local_predict(self._L, float(v), float(g), float(wheelbase), _ptr(q), float(dt)))
+
+    def update(self, zf, R, idf, form="cholesky"):
+        """``idf``: LOCAL landmark ids.  Cholesky form only."""
+        zp = _obs(zf)
+        ids = np.ascontiguousarray(np.asarray(idf, dtype=np.int32).reshape(-1))
+        if ids.shape[0] != zp.shape[0]:
+            raise ValueError("idf and z disagree on the number of observations")
+        r = _small(R)
+        code = SLAM_FORM_JOSEPH if form == "joseph" else SLAM_FORM_CHOLESKY
+        check(self._lib.slam_ekf_local_update(self._L, _ptr(zp), _ptr(ids, C.c_int32), zp.shape[0], _ptr(r), code))
+
+    def add_features(self, zn, R):
+        zp = _obs(zn)
+        if zp.shape[0] == 0:
+            return
+        r = _small(R)
+        check(self._lib.slam_ekf_local_augment(self._L, _ptr(zp), zp.shape[0], _ptr(r)))
+
+    def associate(self, z, R, gate1, gate2):
+        """(zf, idf, zn) against the LOCAL map: idf are local ids."""
+        return self.state.associate(z, R, gate1, gate2)
+
+    def observe(self, z, R, gate1, gate2):
+        """associate on the local state, then update, then add_features; returns the association vector (local ids)."""
+        z = np.asarray(z, dtype=np.float64).reshape(2, -1)
+        assoc = self.state.associate_vector(z, R, gate1, gate2)
+        self.update(z[:, assoc > 0], R, assoc[assoc > 0])
+        self.add_features(z[:, assoc < 0], R)
+        return assoc
 
 
 def _state_of(ref_or_state):

@@ -98,6 +98,22 @@ for T in (Float64, Float32)
         @test a == Int32[1, -1] && length(st) == 7
         @test cov_diag(st) ≈ diag(st.cov) && cov_block(st, 4:5, 1:3) == st.cov[4:5, 1:3]
         @test size(landmark_blocks(st)) == (3, 2) && size(feature_ellipses(st)) == (5, 2)
+
+        # a local area (the compressed EKF): no steps leave the state bit for bit; a step inside equals the step outside
+        x0, P0 = st.x, st.cov
+        ar = LocalArea(st, Int32[2])
+        @test area_info(ar).n0 == 5 && close!(ar) == 3 && st.x == x0 && st.cov == P0
+        ref = EKFSlamState{T}(x0, P0; max_landmarks = 4)
+        ekf_predict!(ref, 4.0, 0.1, 2.0, [0.25 0.0; 0.0 q2], 0.25)
+        open_area!(ar, Int32[2])
+        ekf_predict!(ar, 4.0, 0.1, 2.0, [0.25 0.0; 0.0 q2], 0.25)
+        phi, psi, theta = accumulators(ar)
+        @test size(phi) == (5, 5) && all(iszero, psi) && all(iszero, theta) && global_ids(ar) == Int32[2]
+        close!(ar)
+        @test st.x ≈ ref.x atol = 10tol
+        @test st.cov ≈ ref.cov atol = 100tol
+        open_area!(ar, Int32[1]); abort!(ar)
+        @test landmarks_within(st, st.x[4], st.x[5], 1.0) == Int32[1]
     end
 end
 

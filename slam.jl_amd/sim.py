@@ -148,6 +148,7 @@ class SimLog:
     landmark_tags: object = None                        # sim(nees_every=k): 1-based true landmark behind each map landmark at the end
     best_path: object = None                            # [L, 3]: the best particle's path at the end of the run (a PFSlamState after track_path)
     fixes: list = field(default_factory=list)           # (predict-step index, measured xy) per position fix (sim(fix_every=k))
+    areas: list = field(default_factory=list)           # (observation step, local landmarks, landmarks added, N after) per closed local area (sim(local_radius=r))
 
 
 #: constants of sim/ekfslam-sim.jl:62-76,114
@@ -171,7 +172,7 @@ def default_QR():
 def sim(filt, waypoints: np.ndarray, landmarks: np.ndarray, seed: int, nlaps: int = 2,
         max_steps: int = 100000, monitor=None, fused: bool = False, prune_after=None, merge_gate=None,
         submap_steps=None, association: str = "nearest", nees_every=None, fix_every: int = 0,
-        fix_sigma: float = 0.5) -> SimLog:
+        fix_sigma: float = 0.5, local_radius=None) -> SimLog:
     """The loop of sim/ekfslam-sim.jl:80-141 without sleep/pause.
 
     ``filt`` must already hold the initial state (x = initial pose, P = 0).
@@ -206,7 +207,20 @@ def sim(filt, waypoints: np.ndarray, landmarks: np.ndarray, seed: int, nlaps: in
     position fix -- the true position plus noise of standard deviation ``fix_sigma`` per axis, a GPS receiver -- is applied with
     ``filt.fix_position(xy, fix_sigma^2 I)``.  Its noise comes from a generator of its own (seeded from ``seed``), so every other
     draw of the run is what it is without fixes.  Fixes are recorded in ``log.fixes``.  Not available with ``submap_steps``.
+    ``local_radius``: None (default) changes nothing.  A number r (the compressed EKF, no counterpart in the reference): every
+    predict and observation goes to a local area ``filt.local(filt.landmarks_within(cx, cy, r))`` around the pose (cx, cy) at which
+    it was opened, and ``filt`` itself is brought up to date only when the area is closed: before an observation step at which the
+    vehicle is nearer to the rim than the sensor range plus a margin of LOCAL_MARGIN = 2 m (|pose - centre| + sensor_range + 2 > r:
+    the margin covers the pose error and the landmarks' own, so that nothing the sensor can see lies outside the area), and once
+    more when the course ends.  r must exceed sensor_range + 2.  Up to rounding the run is the plain loop's; ``log.assoc`` holds
+    GLOBAL ids.  Closed areas are recorded in ``log.areas``.  Only with the plain loop's other options at their defaults.
     """
+    if local_radius is not None:
+        if (prune_after is not None or merge_gate is not None or submap_steps is not None or association != "nearest"
+                or nees_every is not None or fix_every):
+            raise ValueError("local_radius is not available together with prune_after, merge_gate, submap_steps, joint "
+                             "association, nees_every or fix_every")
+        return _sim_local(filt, waypoints, landmarks, seed, nlaps, max_steps, monitor, fused, float(local_radius))
     fix_every = int(fix_every)
     if fix_every < 0 or (fix_every and submap_steps is not None):
         raise ValueError("fix_every must be a non-negative step count and is not available with submap_steps")
@@ -306,6 +320,77 @@ def sim(filt, waypoints: np.ndarray, landmarks: np.ndarray, seed: int, nlaps: in
         log.landmark_tags = tags
     if getattr(filt, "path_history", None) is not None:                   # a PFSlamState that tracks its path (FastSLAM.track_path)
         log.best_path = np.array(filt.path())
+    return log
+
+
+LOCAL_MARGIN = 2.0
+
+
+def _sim_local(filt, waypoints, landmarks, seed, nlaps, max_steps, monitor, fused, radius) -> SimLog:
+    """sim(..., local_radius=r): the same vehicle, sensor and draw order as the plain loop; the filter calls go to a local area."""
+    rng = np.random.default_rng(seed)
+    Q, R = default_QR()
+    vehicle = Vehicle(pose=initial_pose(waypoints))
+    if not radius > vehicle.sensor_range + LOCAL_MARGIN:
+        raise ValueError("local_radius must exceed the sensor range plus LOCAL_MARGIN")
+    log = SimLog()
+    dtsum = 0.0
+    nsteps = 0
+
+    def open_area():
+        c = np.asarray(filt.pose(), dtype=float)[:2]
+        return filt.local(filt.landmarks_within(c[0], c[1], radius)), c
+
+    def close_area(area):
+        gids = area.global_ids()
+        added = int(area.info()["added"])
+        area.close()
+        log.areas.append((len(log.obs_steps) - 1, int(gids.size), added, int(filt.N)))
+        area.destroy()
+
+    area, centre = open_area()
+    try:
+        while vehicle.waypoint_id != 0 and nsteps < max_steps:
+            steer(vehicle, waypoints, D_MIN, DT)
+            if vehicle.waypoint_id == 0 and nlaps > 1:
+                vehicle.waypoint_id = 1
+                nlaps -= 1
+            step_vehicle(vehicle, DT)
+            vehicle.measured_speed = vehicle.target_speed + rng.standard_normal() * math.sqrt(Q[0, 0])
+            vehicle.measured_gamma = vehicle.target_gamma + rng.standard_normal() * math.sqrt(Q[1, 1])
+            area.predict(vehicle.measured_speed, vehicle.measured_gamma, vehicle.wheelbase, Q, DT)
+            log.controls.append((vehicle.measured_speed, vehicle.measured_gamma))
+            dtsum += DT
+            if dtsum > DT_OBS:
+                dtsum = 0.0
+                z, _tags = get_observations(vehicle, landmarks, R, rng)
+                pose = np.asarray(area.state.pose(), dtype=float)
+                if math.hypot(pose[0] - centre[0], pose[1] - centre[1]) + vehicle.sensor_range + LOCAL_MARGIN > radius:
+                    close_area(area)
+                    area, centre = open_area()
+                if fused:
+                    assoc = np.asarray(area.observe(z, R, GATE1, GATE2))
+                    idf = assoc[assoc > 0]
+                    zn = np.asarray(z, dtype=float).reshape(2, -1)[:, assoc < 0]
+                else:
+                    zf, idf, zn = area.associate(z, R, GATE1, GATE2)
+                    area.update(zf, R, idf)
+                    area.add_features(zn, R)
+                gids = np.asarray(area.global_ids(), dtype=np.int64)
+                log.obs_steps.append(nsteps)
+                log.observations.append(np.array(z))
+                log.assoc.append((gids[np.asarray(idf, dtype=np.int64).reshape(-1) - 1].tolist(),
+                                  int(np.asarray(zn).reshape(2, -1).shape[1])))
+            nsteps += 1
+            log.true_track.append(np.array(vehicle.pose))
+            log.slam_track.append(np.array(area.state.pose()))
+            if monitor is not None:
+                monitor(vehicle, filt, nsteps)
+        close_area(area)
+        area = None
+    finally:
+        if area is not None:
+            area.destroy()
     return log
 
 
