@@ -22,7 +22,8 @@ export SlamState, EKFSlamState, set_state!, predict, update, add_features, assoc
        CovFactor, factor, factor!, logdet, isposdef, whiten, nees, sample,
        update_linear!, linear_nis, predict_linear!, predict_odometry!, fix_position!, fix_heading!, fix_landmark!,
        step_proposal_unknown!, associate_proposal, proposal_max_obs,
-       LocalArea, open_area!, close!, abort!, landmarks_within, accumulators, area_info, global_ids, local_state
+       LocalArea, open_area!, close!, abort!, landmarks_within, accumulators, area_info, global_ids, local_state,
+       update_iterated!, iterated_nis, observe_iterated!, iterated_limits
 
 const libslamhip = get(ENV, "SLAMHIP_LIB", joinpath(@__DIR__, "libslamhip.so"))
 # the companion library of include/slamhip_frame.h (the rigid frame change); it links against libslamhip.so and lies beside it
@@ -62,6 +63,9 @@ const libslamhip_proposal = get(ENV, "SLAMHIP_PROPOSAL_LIB", joinpath(@__DIR__, 
 # the extension library of include/ext/slamhip_local.h (compressed local-area updates for the EKF), same arrangement (opened at the
 # first LocalArea; it also needs libslamhip_copy.so beside it)
 const libslamhip_local = get(ENV, "SLAMHIP_LOCAL_LIB", joinpath(@__DIR__, "libslamhip_local.so"))
+# the extension library of include/ext/slamhip_iterated.h (the iterated EKF update, relinearised on the device), same arrangement
+# (opened at the first update_iterated! / iterated_nis / iterated_limits)
+const libslamhip_iterated = get(ENV, "SLAMHIP_ITERATED_LIB", joinpath(@__DIR__, "libslamhip_iterated.so"))
 
 const SLAM_OK = Cint(0)
 const SLAM_PF_HALTED = Cint(1)
@@ -648,6 +652,75 @@ fix_position!(s::EKFSlamState, xy, R) = update_linear!(s, unit_rows(length(s), (
 fix_heading!(s::EKFSlamState, phi, var) = update_linear!(s, unit_rows(length(s), (3,)), [phi], fill(Float64(var), 1, 1); wrap = (1,))
 "    fix_landmark!(s, j, xy, R): landmark j was surveyed at xy with covariance R."
 fix_landmark!(s::EKFSlamState, j::Integer, xy, R) = update_linear!(s, unit_rows(length(s), (2 + 2j, 3 + 2j)), xy, R)
+
+# ---- the iterated update (include/ext/slamhip_iterated.h; no counterpart in the reference) ---------------------------------------
+"    iterated_limits() -> (observations per call, iterations per call) as libslamhip_iterated.so reports them."
+function iterated_limits()
+    out = zeros(Int32, 2)
+    check(ccall((:slam_ekf_iterated_limits, libslamhip_iterated), Cint, (Ptr{Int32},), out))
+    Int(out[1]), Int(out[2])
+end
+
+iterated_result(out) = (iterations = Int(out[1]), converged = out[2] != 0, step = out[3], nis = out[4], log_det = out[5],
+                        cost_first = out[9], cost_last = out[10], out = out)
+
+"""
+    update_iterated!(s, z, R, idf; max_iter = 10, tol = 1e-9) -> (iterations, converged, step, nis, log_det, cost_first, cost_last, out)
+
+The iterated EKF update in place on the device (slam_ekf_update_iterated): `ekf_update!` in its Cholesky form with the range-bearing
+model relinearised at every iterate (Gauss-Newton on the MAP cost, WITHOUT a line search) until the largest change of an iterate is
+at most `tol` or `max_iter` (1 .. 64) iterations have run.  `max_iter = 1` is `ekf_update!`.  A call takes at most 8 observations; more
+are applied as consecutive batches of 8 in the order given, each iterated on the state the batch before left: SEQUENTIAL, not the
+joint update of all of them; the result is then the last batch's.  `nothing` for no observation.
+"""
+function update_iterated!(s::EKFSlamState, z::AbstractMatrix, R::AbstractMatrix, idf; max_iter::Integer = 10, tol::Real = 1e-9)
+    m = size(z, 2)
+    ids = Vector{Int32}(vec(collect(idf)))
+    length(ids) == m || throw(ArgumentError("idf and z disagree on the number of observations"))
+    zz, r = pairs64(z), colmajor4(R)
+    res = nothing
+    for lo in 1:8:m
+        hi = min(lo + 7, m)
+        out = zeros(Float64, 10)
+        check(ccall((:slam_ekf_update_iterated, libslamhip_iterated), Cint,
+                    (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Int32}, Cint, Ptr{Cdouble}, Cint, Cdouble, Ptr{Cdouble}),
+                    handle(s), zz[:, lo:hi], ids[lo:hi], hi - lo + 1, r, max_iter, tol, out))
+        res = iterated_result(out)
+    end
+    res
+end
+
+"    iterated_nis(s, z, R, idf; max_iter, tol): what update_iterated! would return; the state is only read (the dry run).  At most 8 observations."
+function iterated_nis(s::EKFSlamState, z::AbstractMatrix, R::AbstractMatrix, idf; max_iter::Integer = 10, tol::Real = 1e-9)
+    m = size(z, 2)
+    ids = Vector{Int32}(vec(collect(idf)))
+    length(ids) == m || throw(ArgumentError("idf and z disagree on the number of observations"))
+    out = zeros(Float64, 10)
+    check(ccall((:slam_ekf_iterated_nis, libslamhip_iterated), Cint,
+                (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Int32}, Cint, Ptr{Cdouble}, Cint, Cdouble, Ptr{Cdouble}),
+                handle(s), pairs64(z), ids, m, colmajor4(R), max_iter, tol, out))
+    iterated_result(out)
+end
+
+"    observe_iterated!(s, z, R, gate1, gate2; max_iter, tol) -> (assoc, result): associate, update_iterated!, augment! in sequence from the host."
+function observe_iterated!(s::EKFSlamState, z::AbstractMatrix, R::AbstractMatrix, gate1::Real, gate2::Real; max_iter::Integer = 10,
+                           tol::Real = 1e-9)
+    zf, idf, zn = associate(s, z, R, gate1, gate2)
+    assoc = zeros(Int32, size(z, 2))
+    hit, new = 0, 0
+    for i in 1:size(z, 2)                                                # the association vector of observe!, from the two lists
+        if hit < size(zf, 2) && z[:, i] == zf[:, hit + 1]
+            hit += 1
+            assoc[i] = idf[hit]
+        elseif new < size(zn, 2) && z[:, i] == zn[:, new + 1]
+            new += 1
+            assoc[i] = -1
+        end
+    end
+    res = update_iterated!(s, zf, R, idf; max_iter = max_iter, tol = tol)
+    augment!(s, zn, R)
+    assoc, res
+end
 
 # ---- compressed local-area updates (include/ext/slamhip_local.h) -----------------------------------------------------------------
 """

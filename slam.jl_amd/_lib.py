@@ -395,6 +395,22 @@ local_lib = Companion("local", LOCAL_SIGNATURES)
 LOCAL_LIB_PATH = local_lib.path
 
 
+# ---- iterated: the iterated EKF update, relinearised on the device, opened at the first such call ----------------------------------
+# Wired like linear, and like it entered in neither table; its surface checks are made by tests/test_iterated_ref_cpu.py.
+SLAM_ITERATED_MAXOBS = 8
+SLAM_ITERATED_MAXITER = 64
+
+#: every symbol include/ext/slamhip_iterated.h declares
+ITERATED_SIGNATURES = {
+    "slam_ekf_update_iterated": (C.c_int, [_h, _dp, _ip, C.c_int, _dp, C.c_int, C.c_double, _dp]),
+    "slam_ekf_iterated_nis": (C.c_int, [_h, _dp, _ip, C.c_int, _dp, C.c_int, C.c_double, _dp]),
+    "slam_ekf_iterated_limits": (C.c_int, [_ip]),
+}
+
+iterated_lib = Companion("iterated", ITERATED_SIGNATURES)
+ITERATED_LIB_PATH = iterated_lib.path
+
+
 def proposal_max_obs() -> int:
     """Observations per call of the proposal step with unknown correspondences, as the library reports it."""
     out = (C.c_int * 4)()

@@ -94,6 +94,19 @@ int slam_between(hipStream_t sd, hipStream_t ss, F body) {
     return SLAM_OK;
 }
 
+// ---- argument checks and copies from host buffers that a call owns ---------------------------------------------------------------
+static inline bool slam_all_finite(const double* a, int cnt) {
+    for (int i = 0; i < cnt; ++i)
+        if (!(a[i] - a[i] == 0.0)) return false;                         // NaN and +-Inf: x - x is NaN
+    return true;
+}
+
+// the stream is drained before the host buffers of an enqueued copy go away, whichever way the call is left
+struct SlamDrainOnExit {
+    hipStream_t s;
+    ~SlamDrainOnExit() { (void)hipStreamSynchronize(s); }
+};
+
 // A/B knobs of the measurement tooling (tile order, workgroups per list, super-row height, the scalar factorisation ...):
 // read from the environment ONLY in the experiments build (`make exp`, libslamhip_exp.so); the product library always
 // takes the default, so no untested code path can be switched on from outside.  What the product library does read:

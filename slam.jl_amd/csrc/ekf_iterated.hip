@@ -1,0 +1,386 @@
+// ekf_iterated.hip -- the iterated EKF update: slam_ekf_update_iterated, slam_ekf_iterated_nis and slam_ekf_iterated_limits
+// (include/ext/slamhip_iterated.h states the rule; tests/iterated_ref.py runs it literally).  libslamhip_iterated.so.
+//
+// H touches the vehicle and the m <= 8 observed landmarks only, and the iterates of those 3 + 2m states depend on P only through
+// the block P[a, a] (at most 19 x 19), so every relinearisation runs inside ONE workgroup and the map is touched once, at the end:
+//     iterated_solve_kernel  (one workgroup)       gathers P[a, a] and x0[a] into LDS and runs the whole Gauss-Newton loop there:
+//                                                   the model at x_i, v_i, S_i, chol, g_i, x_{i+1}, the step, the cost; leaves
+//                                                   C = inv(chol(S)), g, the LAST iteration's Jacobian blocks and `out`
+//     iterated_panel_kernel  (a thread per row r)   PHt[r, :] from P[r, 0:3] (read once) and P[r, f : f + 2] of every DISTINCT
+//                                                   landmark, W1[r, :] = PHt[r, :] C as the handle's dtype, zero-padded to 16
+//                                                   columns, x[r] += PHt[r, :] g
+//     launch_downdate                               P -= W1 W1' on the plain 16-column panel (ekf_syrk.hip), which also keeps Pside
+// The observations travel in one small block copied into the handle's update workspace (Smat, free in the reference form); the
+// solve kernel appends the Jacobian blocks to it, so H never visits the host.  When an S is not positive definite the solve kernel
+// sets the handle's status word: the panel kernel then writes a ZERO panel and leaves x alone, and the down-date returns at once on
+// the same word.
+#include <cmath>
+#include <vector>
+
+#include "common.h"
+#include "../../include/ext/slamhip_iterated.h"
+#include "device_math.h"
+
+int launch_downdate(slam_ekf* h, int kp_total, const void* X, const void* Y, int pitch, const int32_t* dcount, int joseph, int k16,
+                    const void* img);      // ekf_syrk.hip
+
+namespace {
+
+constexpr int MO = SLAM_ITERATED_MAXOBS;                   // 8 observations
+constexpr int LK = 2 * MO;                                 // 16: the panel's columns, one chunk of the down-date
+constexpr int LP = LK + 1;
+constexpr int NA = 3 + 2 * MO;                             // 19: the states H touches
+constexpr int HB = 10;                                     // one observation's Jacobian blocks: Hv (2 x 3, row-major), Hf (2 x 2)
+// the block in Smat, in doubles: z[16], R[4] (column-major), idf as int32[8], then -- written by the solve kernel -- Hv | Hf of
+// the last iteration, [8][10]
+constexpr int B_Z = 0, B_R = LK, B_IDF = B_R + 4, B_H = B_IDF + MO / 2, B_IN = B_H;      // B_H + 80 <= 32 x 32, the smallest Smat
+constexpr int OUTN = 10;
+
+// the model at the reduced iterate xs for observation o: its Jacobian blocks and r = z - zp with the bearing wrapped once
+__device__ __forceinline__ void eval_model(const double* xs, const double* zs, int o, double* hb, double* r) {
+    const ObsModel om = obs_model(xs[0], xs[1], xs[2], xs[3 + 2 * o], xs[4 + 2 * o]);
+#pragma unroll
+    for (int q = 0; q < 6; ++q) hb[q] = om.Hv[q];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) hb[6 + q] = om.Hf[q];
+    r[0] = zs[2 * o] - om.zp[0];
+    r[1] = mpi_to_pi_d(zs[2 * o + 1] - om.zp[1]);
+}
+
+// row t of the reduced H (k x na) times a reduced vector u: the row's five non-zeros
+__device__ __forceinline__ double h_row_dot(const double* hbo, int o, int q, const double* u) {
+    const double* hv = hbo + 3 * q;
+    const double* hf = hbo + 6 + 2 * q;
+    return __builtin_fma(hf[1], u[4 + 2 * o], __builtin_fma(hf[0], u[3 + 2 * o], __builtin_fma(hv[2], u[2], __builtin_fma(hv[1], u[1], hv[0] * u[0]))));
+}
+
+// One workgroup of 256.  Thread (i, j) forms S[i][j] and owns that entry in the trailing updates of the factorisation; lane r of the
+// first 16 scales row r of a pivot's column and owns column r of inv(L).  Rows / columns >= k are the identity, so the chain of
+// pivots stops at k.  Every decision (a failing pivot, the stop) is taken from values all threads read from LDS, so it is uniform.
+// status may be null (the dry run).
+template <typename T>
+__global__ __launch_bounds__(256) void iterated_solve_kernel(const T* __restrict__ x, const T* __restrict__ P, int ld, double* __restrict__ blob,
+                                                              int m, int max_iter, double tol, double* __restrict__ Cout,
+                                                              double* __restrict__ gout, double* __restrict__ out, int32_t* __restrict__ status) {
+    constexpr int L = kTileLog2<T>;
+    __shared__ double Pa[NA][NA + 1], PaHt[NA][LP], M[LK][LP], S0[LK][LP], Li[LK][LP];
+    __shared__ double x0a[NA], xi[NA], xn[NA], du[NA], v[LK], y[LK], g[LK], pr[LK], rr[2][LK], hb[2][MO][HB], zs[LK], Rs[4];
+    __shared__ int cols[NA];
+    const int tid = threadIdx.x, k = 2 * m, na = 3 + 2 * m;
+    const int32_t* __restrict__ idf = reinterpret_cast<const int32_t*>(blob + B_IDF);
+    if (tid < NA) cols[tid] = tid < 3 ? tid : (tid < na ? 3 + 2 * (idf[(tid - 3) >> 1] - 1) + ((tid - 3) & 1) : 0);
+    if (tid < LK) zs[tid] = tid < k ? blob[B_Z + tid] : 0.0;
+    if (tid < 4) Rs[tid] = blob[B_R + tid];
+    __syncthreads();
+    for (int t = tid; t < na * na; t += 256) {
+        const int r = t / na, c = t - r * na;
+        Pa[r][c] = (double)sym_at(P, ld, L, cols[r], cols[c]);
+    }
+    if (tid < na) x0a[tid] = xi[tid] = (double)x[cols[tid]];
+    __syncthreads();
+    if (tid < m) eval_model(xi, zs, tid, hb[0][tid], &rr[0][2 * tid]);
+    __syncthreads();
+    const double rdet = 1.0 / (Rs[0] * Rs[3] - Rs[1] * Rs[2]);
+    const int i = tid >> 4, j = tid & 15;
+    int b = 0, it = 0, conv = 0, fail = -1;
+    double step = 0.0, nis = 0.0, lsum = 0.0, lmin = 0.0, piv = 0.0, Jfirst = 0.0, Jlast = 0.0;
+    for (;;) {
+        if (tid < na) du[tid] = x0a[tid] - xi[tid];
+        __syncthreads();
+        if (tid < k) v[tid] = rr[b][tid] - h_row_dot(hb[b][tid >> 1], tid >> 1, tid & 1, du);      // v = r - H (x0 - x_i)
+        for (int t = tid; t < na * LK; t += 256) {                              // P[a, a] H'
+            const int r = t >> 4, c = t & 15;
+            PaHt[r][c] = c < k ? h_row_dot(hb[b][c >> 1], c >> 1, c & 1, Pa[r]) : 0.0;
+        }
+        __syncthreads();
+        {
+            double s = i == j ? 1.0 : 0.0;
+            if (i < k && j < k) {
+                const int o = i >> 1, q = i & 1;
+                const double* hv = hb[b][o] + 3 * q;
+                const double* hf = hb[b][o] + 6 + 2 * q;
+                s = __builtin_fma(hf[1], PaHt[4 + 2 * o][j], __builtin_fma(hf[0], PaHt[3 + 2 * o][j],
+                    __builtin_fma(hv[2], PaHt[2][j], __builtin_fma(hv[1], PaHt[1][j], hv[0] * PaHt[0][j]))));
+                if ((i >> 1) == (j >> 1)) s += Rs[(j & 1) * 2 + (i & 1)];
+            }
+            M[i][j] = s;
+        }
+        __syncthreads();
+        const double sym = (M[i][j] + M[j][i]) * 0.5;                         // S = (S + S') / 2
+        __syncthreads();
+        M[i][j] = sym;
+        S0[i][j] = sym;
+        __syncthreads();
+        // right-looking Cholesky S = L L'; every thread reads the same pivot
+        // (the same pivots and the same arithmetic per entry as linear_factor_kernel; the trailing update of a pivot is one
+        //  multiply-add per THREAD instead of a loop per lane -- the chain of k pivots is what an iteration costs -- and log det S
+        //  is taken from the factor's diagonal once, after the last iteration)
+        lmin = INFINITY;
+        for (int c = 0; c < k; ++c) {
+            piv = M[c][c];
+            if (!(piv > 0.0) || !(piv < INFINITY)) { fail = c; break; }
+            const double d = sqrt(piv);
+            lmin = d < lmin ? d : lmin;
+            __syncthreads();
+            if (tid >= c && tid < LK) M[tid][c] = M[tid][c] / d;
+            __syncthreads();
+            if (i > c && j > c && j <= i) M[i][j] -= M[i][c] * M[j][c];
+            __syncthreads();
+        }
+        if (fail >= 0) break;
+        if (tid < k) {       // inv(L): lane c solves L X[:, c] = e_c
+            for (int r = 0; r < k; ++r) {
+                double s = r == tid ? 1.0 : 0.0;
+                for (int q = tid; q < r; ++q) s -= M[r][q] * Li[q][tid];
+                Li[r][tid] = r < tid ? 0.0 : s / M[r][r];
+            }
+        }
+        __syncthreads();
+        if (tid < k) {       // y = C' v = inv(L) v
+            double s = 0.0;
+            for (int q = 0; q <= tid; ++q) s += Li[tid][q] * v[q];
+            y[tid] = s;
+        }
+        __syncthreads();
+        if (tid < LK) {      // g = C y = inv(L)' y
+            double s = 0.0;
+            for (int q = tid; q < k; ++q) s += Li[q][tid] * y[q];
+            g[tid] = s;
+        }
+        __syncthreads();
+        if (tid < na) {      // x_{i+1} = x0 + P[a, a] H' g
+            double s = 0.0;
+            for (int q = 0; q < k; ++q) s += PaHt[tid][q] * g[q];
+            xn[tid] = x0a[tid] + s;
+        }
+        if (tid >= 64 && tid < 64 + LK) {      // the prior's share of the cost, row by row: g_t ((S - I (x) R) g)_t
+            const int t = tid - 64;
+            double s = 0.0;
+            if (t < k)
+                for (int q = 0; q < k; ++q) s += (S0[t][q] - ((t >> 1) == (q >> 1) ? Rs[(q & 1) * 2 + (t & 1)] : 0.0)) * g[q];
+            pr[t] = t < k ? g[t] * s : 0.0;
+        }
+        __syncthreads();
+        if (tid < m) eval_model(xn, zs, tid, hb[b ^ 1][tid], &rr[b ^ 1][2 * tid]);      // the cost's residuals; the next iteration's model
+        step = 0.0;
+        for (int r = 0; r < na; ++r) {
+            const double d = fabs(xn[r] - xi[r]);
+            step = d > step ? d : step;
+        }
+        nis = 0.0;
+        for (int q = 0; q < k; ++q) nis += y[q] * y[q];
+        __syncthreads();
+        double J = 0.0;
+        for (int q = 0; q < k; ++q) J += pr[q];
+        for (int o = 0; o < m; ++o) {
+            const double r0 = rr[b ^ 1][2 * o], r1 = rr[b ^ 1][2 * o + 1];
+            J += (Rs[3] * r0 * r0 - (Rs[1] + Rs[2]) * r0 * r1 + Rs[0] * r1 * r1) * rdet;
+        }
+        if (it == 0) Jfirst = J;
+        Jlast = J;
+        ++it;
+        conv = step <= tol;
+        if (conv || it == max_iter) break;
+        if (tid < na) xi[tid] = xn[tid];
+        b ^= 1;
+        __syncthreads();
+    }
+    if (fail >= 0) {
+        if (tid == 0) {
+            out[0] = (double)it; out[1] = 0.0; out[2] = step; out[3] = 0.0; out[4] = 0.0; out[5] = piv; out[6] = (double)fail;
+            out[7] = (double)it; out[8] = Jfirst; out[9] = Jlast;
+            if (status) status[0] = 1;
+        }
+        return;
+    }
+    Cout[tid] = (i < k && j < k && i <= j) ? Li[j][i] : 0.0;            // C[i][j] = inv(L)[j][i], zero outside the leading k x k
+    if (tid < LK) gout[tid] = tid < k ? g[tid] : 0.0;
+    if (tid < m * HB) blob[B_H + tid] = hb[b][tid / HB][tid % HB];       // the Jacobian of the LAST iteration, for the panel
+    if (tid == 0) {
+        for (int c = 0; c < k; ++c) lsum += log(M[c][c]);                 // the last iteration's factor is still in M
+        out[0] = (double)it; out[1] = conv ? 1.0 : 0.0; out[2] = step; out[3] = nis; out[4] = 2.0 * lsum; out[5] = lmin; out[6] = -1.0;
+        out[7] = -1.0; out[8] = Jfirst; out[9] = Jlast;
+        if (status) status[0] = 0;
+    }
+}
+
+// One thread per row r of the PANEL (npad rows: the rows >= n are written as zero, the down-date has no row guards), one wave a
+// workgroup so that the rows are spread over the CUs.  Consecutive threads read consecutive rows of one column of a column-major
+// tile wherever (r, f) lies on or below the diagonal tiles -- the access pattern of the product update's pht_body.  A row reads
+// P[r, 0:3] once and the pair P[r, f : f + 2] once per DISTINCT landmark, every load issued before the first use.
+constexpr int PANEL_THREADS = 64;
+
+template <typename T>
+__global__ __launch_bounds__(PANEL_THREADS) void iterated_panel_kernel(T* __restrict__ x, const T* __restrict__ P, int ld, int n, int npad,
+                                                                        const double* __restrict__ blob, int m, const double* __restrict__ Cin,
+                                                                        const double* __restrict__ gin, T* __restrict__ W1, int pitchW,
+                                                                        const int32_t* __restrict__ status) {
+    constexpr int L = kTileLog2<T>;
+    __shared__ double Cs[LK * LK], gs[LK], hs[MO * HB];
+    __shared__ int fu[MO], slot[MO], nds;
+    const bool bad = status[0] != 0;                                      // (uniform)
+    if (!bad) {
+        for (int t = threadIdx.x; t < LK * LK; t += PANEL_THREADS) Cs[t] = Cin[t];
+        if (threadIdx.x < LK) gs[threadIdx.x] = gin[threadIdx.x];
+        for (int t = threadIdx.x; t < m * HB; t += PANEL_THREADS) hs[t] = blob[B_H + t];
+    }
+    if (threadIdx.x == 0) {                                               // the distinct landmarks, in the order of their first mention
+        const int32_t* __restrict__ idf = reinterpret_cast<const int32_t*>(blob + B_IDF);
+        int nd = 0;
+        for (int o = 0; o < MO; ++o) {
+            int s = 0;
+            if (o < m) {
+                const int f = 3 + 2 * (idf[o] - 1);
+                for (s = 0; s < nd && fu[s] != f; ++s) {}
+                if (s == nd) fu[nd++] = f;
+            }
+            slot[o] = s;
+        }
+        for (int s = nd; s < MO; ++s) fu[s] = fu[0];
+        nds = nd;
+    }
+    __syncthreads();
+    const int r = blockIdx.x * PANEL_THREADS + threadIdx.x;
+    if (r >= npad) return;
+    T* __restrict__ w = W1 + (size_t)r * pitchW;
+    if (bad || r >= n) {
+#pragma unroll
+        for (int c = 0; c < LK; ++c) w[c] = (T)0;
+        return;
+    }
+    const int nd = nds;
+    const T t0 = P[p_off(ld, L, r, 0)], t1 = P[p_off(ld, L, r, 1)], t2 = P[p_off(ld, L, r, 2)];
+    T q0[MO], q1[MO];
+#pragma unroll
+    for (int s = 0; s < MO; ++s) {
+        q0[s] = (T)0;
+        q1[s] = (T)0;
+        if (s < nd) {
+            q0[s] = sym_at(P, ld, L, r, fu[s]);                           // P[r, f]: from row f where (r, f) lies above the diagonal tiles
+            q1[s] = sym_at(P, ld, L, r, fu[s] + 1);
+        }
+    }
+    const double xr = (double)x[r];
+    const double p0 = (double)t0, p1 = (double)t1, p2 = (double)t2;
+    double dxr = 0.0, acc[LK];
+#pragma unroll
+    for (int c = 0; c < LK; ++c) acc[c] = 0.0;
+#pragma unroll
+    for (int o = 0; o < MO; ++o) {
+        if (o < m) {
+            const int s = slot[o];
+            T a0 = q0[0], a1 = q1[0];
+#pragma unroll
+            for (int u = 1; u < MO; ++u) {                                // the landmark's pair, by selects: the registers stay registers
+                a0 = s == u ? q0[u] : a0;
+                a1 = s == u ? q1[u] : a1;
+            }
+            const double* hbo = hs + o * HB;
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                const double* hv = hbo + 3 * q;
+                const double* hf = hbo + 6 + 2 * q;
+                const double pht = __builtin_fma(hf[1], (double)a1, __builtin_fma(hf[0], (double)a0,
+                                   __builtin_fma(hv[2], p2, __builtin_fma(hv[1], p1, hv[0] * p0))));
+                const int row = 2 * o + q;
+#pragma unroll
+                for (int c = 0; c < LK; ++c) acc[c] += pht * Cs[row * LK + c];      // C is upper: zero below the diagonal
+                dxr += pht * gs[row];
+            }
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < LK; ++c) w[c] = (T)acc[c];
+    x[r] = (T)(xr + dxr);
+}
+
+// every rule of the header; fills the block.  h is dereferenced only after the rules that need no state
+int check_arguments(slam_ekf* h, const double* zf, const int32_t* idf, int m, const double* R, int max_iter, double tol, const double* out,
+                    std::vector<double>& blob) {
+    ARG_CHECK(h != nullptr, "null handle");
+    ARG_CHECK(zf != nullptr && idf != nullptr && R != nullptr && out != nullptr, "null argument");
+    ARG_CHECK(m >= 1 && m <= SLAM_ITERATED_MAXOBS, "m outside 1 .. SLAM_ITERATED_MAXOBS");
+    ARG_CHECK(max_iter >= 1 && max_iter <= SLAM_ITERATED_MAXITER, "max_iter outside 1 .. 64");
+    ARG_CHECK(std::isfinite(tol) && tol >= 0.0, "tol is negative or not finite");
+    ARG_CHECK(slam_all_finite(zf, 2 * m), "zf is not finite");
+    ARG_CHECK(slam_all_finite(R, 4), "R is not finite");
+    ARG_CHECK(R[1] == R[2], "R is not symmetric");
+    ARG_CHECK(R[0] > 0.0 && R[0] * R[3] - R[1] * R[2] > 0.0, "R is not positive definite");
+    blob.assign(B_IN, 0.0);
+    int32_t* words = reinterpret_cast<int32_t*>(blob.data() + B_IDF);
+    for (int o = 0; o < MO; ++o) words[o] = 1;
+    for (int o = 0; o < m; ++o) {
+        ARG_CHECK(idf[o] >= 1 && idf[o] <= h->N, "idf entry out of range (Julia: BoundsError)");
+        words[o] = idf[o];
+        blob[B_Z + 2 * o] = zf[2 * o];
+        blob[B_Z + 2 * o + 1] = zf[2 * o + 1];
+    }
+    for (int q = 0; q < 4; ++q) blob[B_R + q] = R[q];
+    return SLAM_OK;
+}
+
+template <typename T>
+int enqueue(slam_ekf* h, int m, int max_iter, double tol, bool commit) {
+    const int n = 3 + 2 * h->N;
+    double* blob = h->Smat;
+    {
+        KTimer t(h, SLAM_K_FACTOR);
+        hipLaunchKernelGGL(iterated_solve_kernel<T>, dim3(1), dim3(256), 0, h->stream, (const T*)h->x, (const T*)h->P, h->ld, blob, m, max_iter,
+                           tol, h->Cmat, h->gvec, h->d_small, commit ? h->d_status : (int32_t*)nullptr);
+    }
+    HIP_TRY(hipGetLastError());
+    if (!commit) return SLAM_OK;
+    {
+        KTimer t(h, SLAM_K_W1);
+        hipLaunchKernelGGL(iterated_panel_kernel<T>, dim3((h->npad + PANEL_THREADS - 1) / PANEL_THREADS), dim3(PANEL_THREADS), 0, h->stream,
+                           (T*)h->x, (const T*)h->P, h->ld, n, h->npad, (const double*)blob, m, (const double*)h->Cmat,
+                           (const double*)h->gvec, (T*)h->W1, 2 * h->kcap, (const int32_t*)h->d_status);
+    }
+    HIP_TRY(hipGetLastError());
+    return launch_downdate(h, LK, h->W1, h->W1, 2 * h->kcap, (const int32_t*)nullptr, 0, LK, nullptr);
+}
+
+int iterated_call(slam_ekf* h, const double* zf, const int32_t* idf, int m, const double* R, int max_iter, double tol, double* out,
+                  bool commit) {
+    std::vector<double> blob;
+    int rc;
+    if ((rc = check_arguments(h, zf, idf, m, R, max_iter, tol, out, blob))) return rc;
+    HIP_TRY(hipSetDevice(h->device));
+    if ((rc = ensure_update_workspace(h, MO))) return rc;                 // kcap >= 32: Smat holds the block, W1 16 columns
+    SlamDrainOnExit drain{h->stream};
+    HIP_TRY(hipMemcpyAsync(h->Smat, blob.data(), sizeof(double) * B_IN, hipMemcpyHostToDevice, h->stream));
+    rc = h->dtype == SLAM_F32 ? enqueue<float>(h, m, max_iter, tol, commit) : enqueue<double>(h, m, max_iter, tol, commit);
+    if (rc) return rc;
+    if (commit) h->grid_force = 1;                                        // the means moved: the grid is rebuilt at the next query
+    HIP_TRY(hipMemcpyAsync(h->h_small, h->d_small, sizeof(double) * OUTN, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    for (int q = 0; q < OUTN; ++q) out[q] = h->h_small[q];
+    if (out[6] >= 0.0) {
+        slam_set_error("iterated update: S is not positive definite at iteration %d, pivot %d is %g (state left unchanged)", (int)out[7],
+                       (int)out[6], out[5]);
+        return SLAM_E_NOTPD;
+    }
+    return SLAM_OK;
+}
+
+}  // namespace
+
+extern "C" int slam_ekf_update_iterated(slam_ekf_t h, const double* zf, const int32_t* idf, int m, const double R[4], int max_iter,
+                                        double tol, double out[10]) {
+    SLAM_RANGE();
+    return iterated_call(h, zf, idf, m, R, max_iter, tol, out, true);
+}
+
+extern "C" int slam_ekf_iterated_nis(slam_ekf_t h, const double* zf, const int32_t* idf, int m, const double R[4], int max_iter, double tol,
+                                     double out[10]) {
+    SLAM_RANGE();
+    return iterated_call(h, zf, idf, m, R, max_iter, tol, out, false);
+}
+
+extern "C" int slam_ekf_iterated_limits(int32_t out[2]) {
+    SLAM_RANGE();
+    ARG_CHECK(out != nullptr, "null argument");
+    out[0] = SLAM_ITERATED_MAXOBS;
+    out[1] = SLAM_ITERATED_MAXITER;
+    return SLAM_OK;
+}

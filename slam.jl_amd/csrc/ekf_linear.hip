@@ -282,12 +282,6 @@ __global__ __launch_bounds__(256) void linear_strip_kernel(T* __restrict__ x, T*
     x[2] = (T)xn[2];
 }
 
-bool all_finite(const double* a, int cnt) {
-    for (int i = 0; i < cnt; ++i)
-        if (!std::isfinite(a[i])) return false;
-    return true;
-}
-
 // every rule of the header that the host can decide; fills the blob.  h is dereferenced only after the rules that need no state
 int check_measurement(slam_ekf* h, int k, const int32_t* ptr, const int32_t* idx, const double* val, const double* z, const double* R,
                       int mode, uint32_t wrap_mask, const double* out, std::vector<double>& blob) {
@@ -313,8 +307,8 @@ int check_measurement(slam_ekf* h, int k, const int32_t* ptr, const int32_t* idx
         }
         words[i + 1] = ptr[i + 1];
     }
-    ARG_CHECK(all_finite(z, k), "z is not finite");
-    ARG_CHECK(all_finite(R, k * k), "R is not finite");
+    ARG_CHECK(slam_all_finite(z, k), "z is not finite");
+    ARG_CHECK(slam_all_finite(R, k * k), "R is not finite");
     for (int i = 0; i < k; ++i) {
         ARG_CHECK(R[i * k + i] >= 0.0, "R has a negative diagonal");
         for (int j = 0; j < k; ++j) {
@@ -325,12 +319,6 @@ int check_measurement(slam_ekf* h, int k, const int32_t* ptr, const int32_t* idx
     }
     return SLAM_OK;
 }
-
-// the stream is drained before the host buffers of an enqueued copy go away, whichever way the call is left
-struct DrainOnExit {
-    hipStream_t s;
-    ~DrainOnExit() { (void)hipStreamSynchronize(s); }
-};
 
 template <typename T>
 int enqueue_front(slam_ekf* h, int k, int mode, uint32_t wrap, bool commit) {
@@ -360,7 +348,7 @@ int linear_call(slam_ekf* h, int k, const int32_t* ptr, const int32_t* idx, cons
     if ((rc = check_measurement(h, k, ptr, idx, val, z, R, mode, wrap_mask, out, blob))) return rc;
     HIP_TRY(hipSetDevice(h->device));
     if ((rc = ensure_update_workspace(h, SLAM_LINEAR_MAXROWS / 2))) return rc;      // kcap >= 32: Smat holds the blob, W1 16 columns
-    DrainOnExit drain{h->stream};
+    SlamDrainOnExit drain{h->stream};
     HIP_TRY(hipMemcpyAsync(h->Smat, blob.data(), sizeof(double) * B_DOUBLES, hipMemcpyHostToDevice, h->stream));
     rc = h->dtype == SLAM_F32 ? enqueue_front<float>(h, k, mode, wrap_mask, commit) : enqueue_front<double>(h, k, mode, wrap_mask, commit);
     if (rc) return rc;
@@ -410,7 +398,7 @@ extern "C" int slam_ekf_linear_nis(slam_ekf_t h, int k, const int32_t* ptr, cons
 extern "C" int slam_ekf_predict_linear(slam_ekf_t h, const double* xv, const double* Gv, const double* Qv) {
     SLAM_RANGE();
     ARG_CHECK(h != nullptr && xv != nullptr && Gv != nullptr && Qv != nullptr, "null argument");
-    ARG_CHECK(all_finite(xv, 3) && all_finite(Gv, 9) && all_finite(Qv, 9), "a value is not finite");
+    ARG_CHECK(slam_all_finite(xv, 3) && slam_all_finite(Gv, 9) && slam_all_finite(Qv, 9), "a value is not finite");
     StripArgs A;
     memcpy(A.xv, xv, sizeof(A.xv));
     memcpy(A.G, Gv, sizeof(A.G));
@@ -422,7 +410,7 @@ extern "C" int slam_ekf_predict_linear(slam_ekf_t h, const double* xv, const dou
 extern "C" int slam_ekf_predict_odometry(slam_ekf_t h, const double* d, const double* Q3) {
     SLAM_RANGE();
     ARG_CHECK(h != nullptr && d != nullptr && Q3 != nullptr, "null argument");
-    ARG_CHECK(all_finite(d, 3) && all_finite(Q3, 9), "a value is not finite");
+    ARG_CHECK(slam_all_finite(d, 3) && slam_all_finite(Q3, 9), "a value is not finite");
     StripArgs A;
     memset(&A, 0, sizeof(A));
     memcpy(A.xv, d, sizeof(A.xv));

@@ -37,7 +37,7 @@ __all__ = [
     "find_duplicates", "merge_features", "merge_features_", "merge_in_batches",
     "chi2_table", "associate_joint", "observe_joint",
     "copy_state", "select_features", "select_map", "grown_capacity",
-    "CovarianceFactor", "linear_rows", "LocalArea",
+    "CovarianceFactor", "linear_rows", "LocalArea", "IteratedResult",
 ]
 
 _DTYPES = {"f32": (SLAM_F32, np.float32), "f64": (SLAM_F64, np.float64),
@@ -262,6 +262,28 @@ _CHI2_CACHE = {}                    # confidence -> the longest table computed s
 
 
 JC_INFO_KEYS = ("pairings", "d2", "tests", "exhausted", "truncated", "candidates", "deepest")
+
+
+class IteratedResult:
+    """What an iterated update reports (slam_ekf_update_iterated, include/ext/slamhip_iterated.h): ``iterations`` run, ``converged``
+    (the last step was <= tol), the last ``step``, ``nis`` = v' inv(S) v and ``log_det`` of S at the last iteration, the MAP cost after
+    the first iteration (``cost_first``) and after the last (``cost_last``), and ``out``, the ten numbers as the library wrote them.
+    ``batches``: the results of every batch of a call that took more than 8 observations, this one last."""
+
+    def __init__(self, out):
+        self.out = np.array(out, dtype=np.float64)
+        self.iterations = int(self.out[0])
+        self.converged = bool(self.out[1])
+        self.step = float(self.out[2])
+        self.nis = float(self.out[3])
+        self.log_det = float(self.out[4])
+        self.cost_first = float(self.out[8])
+        self.cost_last = float(self.out[9])
+        self.batches = (self,)
+
+    def __repr__(self):
+        return (f"IteratedResult(iterations={self.iterations}, converged={self.converged}, step={self.step:.3g}, nis={self.nis:.6g}, "
+                f"cost_first={self.cost_first:.6g}, cost_last={self.cost_last:.6g})")
 
 
 class SlamState:
@@ -784,6 +806,60 @@ class EKFSlamState(SlamState):
         """Landmark ``b`` lies ``dxy`` from landmark ``a`` (1-based), with covariance ``R`` (0: exactly)."""
         fa, fb = 3 + 2 * (int(a) - 1), 3 + 2 * (int(b) - 1)
         return self.update_linear([{fb: 1.0, fa: -1.0}, {fb + 1: 1.0, fa + 1: -1.0}], dxy, R)
+
+    # -- the iterated update (libslamhip_iterated.so, include/ext/slamhip_iterated.h) -------------------------------------
+    def _iterated(self, fn, zp, ids, r, max_iter, tol):
+        out = np.zeros(10)
+        check(fn(self._h, _ptr(zp), _ptr(ids, C.c_int32), zp.shape[0], _ptr(r), int(max_iter), float(tol), _ptr(out)))
+        return IteratedResult(out)
+
+    def update_iterated(self, zf, R, idf, max_iter=10, tol=1e-9):
+        """The iterated EKF update (slam_ekf_update_iterated): ``update`` in its Cholesky form with the range-bearing model
+        relinearised at every iterate -- Gauss-Newton on the MAP cost, WITHOUT a line search -- until the largest change of an
+        iterate is at most ``tol`` or ``max_iter`` (1 .. 64) iterations have run; every iteration runs on the device and the map is
+        touched once, at the end.  ``max_iter=1`` is ``update``.  Returns an :class:`IteratedResult` (iterations, converged, step,
+        nis, cost_first, cost_last); raises NotPositiveDefinite with the state unchanged.
+        A call takes at most 8 observations.  More are applied as consecutive batches of 8 in the order given, each iterated on the
+        state the batch before it left: that is SEQUENTIAL and is not the joint update of all of them.  The result is then the
+        last batch's, and its ``batches`` lists every batch's.  No observation: nothing is done and None is returned."""
+        zp = _obs(zf)
+        ids = np.ascontiguousarray(np.asarray(idf, dtype=np.int32).reshape(-1))
+        if ids.shape[0] != zp.shape[0]:
+            raise ValueError("idf and z disagree on the number of observations")
+        if zp.shape[0] == 0:
+            return None
+        r = _small(R)
+        fn = _lib.iterated_lib().slam_ekf_update_iterated
+        B = _lib.SLAM_ITERATED_MAXOBS
+        done = []
+        for s in range(0, zp.shape[0], B):
+            done.append(self._iterated(fn, np.ascontiguousarray(zp[s:s + B]), np.ascontiguousarray(ids[s:s + B]), r, max_iter, tol))
+        done[-1].batches = tuple(done)
+        return done[-1]
+
+    def iterated_nis(self, zf, R, idf, max_iter=10, tol=1e-9):
+        """What ``update_iterated`` would return, with the state only read (slam_ekf_iterated_nis): the dry run that tells whether
+        the iteration converges and lowers the cost (``cost_last`` against ``cost_first``) before it is committed.  At most 8
+        observations: a second batch would have to start from the state the first one leaves."""
+        zp = _obs(zf)
+        ids = np.ascontiguousarray(np.asarray(idf, dtype=np.int32).reshape(-1))
+        if ids.shape[0] != zp.shape[0]:
+            raise ValueError("idf and z disagree on the number of observations")
+        if zp.shape[0] > _lib.SLAM_ITERATED_MAXOBS:
+            raise ValueError("iterated_nis takes at most 8 observations")
+        res = self._iterated(_lib.iterated_lib().slam_ekf_iterated_nis, zp, ids, _small(R), max_iter, tol)
+        res.batches = (res,)
+        return res
+
+    def observe_iterated(self, z, R, gate1, gate2, max_iter=10, tol=1e-9):
+        """associate -> update_iterated -> add_features (sim/ekfslam-sim.jl:114-120 with the iterated update), the three calls in
+        sequence from the host.  Returns ``(assoc, result)``: the association vector (see associate_vector) and what
+        ``update_iterated`` returned (None when nothing was matched)."""
+        z = np.asarray(z, dtype=np.float64).reshape(2, -1)
+        assoc = self.associate_vector(z, R, gate1, gate2)
+        res = self.update_iterated(z[:, assoc > 0], R, assoc[assoc > 0], max_iter=max_iter, tol=tol)
+        self.add_features(z[:, assoc < 0], R)
+        return assoc, res
 
     def transform(self, tx, ty, theta):
         """Express the whole state in another frame, in place on the device (slam_ekf_transform): every position becomes

@@ -172,7 +172,7 @@ def default_QR():
 def sim(filt, waypoints: np.ndarray, landmarks: np.ndarray, seed: int, nlaps: int = 2,
         max_steps: int = 100000, monitor=None, fused: bool = False, prune_after=None, merge_gate=None,
         submap_steps=None, association: str = "nearest", nees_every=None, fix_every: int = 0,
-        fix_sigma: float = 0.5, local_radius=None) -> SimLog:
+        fix_sigma: float = 0.5, local_radius=None, iterated=None) -> SimLog:
     """The loop of sim/ekfslam-sim.jl:80-141 without sleep/pause.
 
     ``filt`` must already hold the initial state (x = initial pose, P = 0).
@@ -214,7 +214,16 @@ def sim(filt, waypoints: np.ndarray, landmarks: np.ndarray, seed: int, nlaps: in
     the margin covers the pose error and the landmarks' own, so that nothing the sensor can see lies outside the area), and once
     more when the course ends.  r must exceed sensor_range + 2.  Up to rounding the run is the plain loop's; ``log.assoc`` holds
     GLOBAL ids.  Closed areas are recorded in ``log.areas``.  Only with the plain loop's other options at their defaults.
+    ``iterated``: None (default) changes nothing.  An integer k (the iterated EKF, no counterpart in the reference): the update of
+    every observation step is ``filt.update_iterated(zf, R, idf, max_iter=k)`` -- relinearised up to k times, more than 8 matched
+    observations in consecutive batches of 8 -- after the nearest-neighbour association; with ``fused`` the three calls are
+    ``filt.observe_iterated``.  Not available with joint association, ``submap_steps`` or ``local_radius``.
     """
+    if iterated is not None:
+        iterated = int(iterated)
+        if iterated < 1 or association != "nearest" or submap_steps is not None or local_radius is not None:
+            raise ValueError("iterated must be a positive iteration count and is not available with joint association, "
+                             "submap_steps or local_radius")
     if local_radius is not None:
         if (prune_after is not None or merge_gate is not None or submap_steps is not None or association != "nearest"
                 or nees_every is not None or fix_every):
@@ -260,12 +269,18 @@ def sim(filt, waypoints: np.ndarray, landmarks: np.ndarray, seed: int, nlaps: in
             dtsum = 0.0
             z, ztags = get_observations(vehicle, landmarks, R, rng)       # :108
             if fused:
-                assoc = np.asarray(filt.observe_joint(z, R, GATE1, GATE2)[0] if joint else filt.observe(z, R, GATE1, GATE2))   # :114-120 in one call
+                if iterated is not None:
+                    assoc = np.asarray(filt.observe_iterated(z, R, GATE1, GATE2, max_iter=iterated)[0])
+                else:
+                    assoc = np.asarray(filt.observe_joint(z, R, GATE1, GATE2)[0] if joint else filt.observe(z, R, GATE1, GATE2))   # :114-120 in one call
                 idf = assoc[assoc > 0]
                 zn = np.asarray(z, dtype=float).reshape(2, -1)[:, assoc < 0]
             else:
                 zf, idf, zn = filt.associate_joint(z, R, GATE1, GATE2)[:3] if joint else filt.associate(z, R, GATE1, GATE2)   # :114
-                filt.update(zf, R, idf)                                   # :117
+                if iterated is not None:
+                    filt.update_iterated(zf, R, idf, max_iter=iterated)
+                else:
+                    filt.update(zf, R, idf)                               # :117
                 filt.add_features(zn, R)                                  # :120
             log.obs_steps.append(nsteps)
             log.observations.append(np.array(z))
