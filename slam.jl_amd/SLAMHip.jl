@@ -23,7 +23,8 @@ export SlamState, EKFSlamState, set_state!, predict, update, add_features, assoc
        update_linear!, linear_nis, predict_linear!, predict_odometry!, fix_position!, fix_heading!, fix_landmark!,
        step_proposal_unknown!, associate_proposal, proposal_max_obs,
        LocalArea, open_area!, close!, abort!, landmarks_within, accumulators, area_info, global_ids, local_state,
-       update_iterated!, iterated_nis, observe_iterated!, iterated_limits
+       update_iterated!, iterated_nis, observe_iterated!, iterated_limits,
+       FirstEstimates, fej, predict!, update!, reset!, remap!, linearisation, set_linearisation!, fej_limits
 
 const libslamhip = get(ENV, "SLAMHIP_LIB", joinpath(@__DIR__, "libslamhip.so"))
 # the companion library of include/slamhip_frame.h (the rigid frame change); it links against libslamhip.so and lies beside it
@@ -66,6 +67,9 @@ const libslamhip_local = get(ENV, "SLAMHIP_LOCAL_LIB", joinpath(@__DIR__, "libsl
 # the extension library of include/ext/slamhip_iterated.h (the iterated EKF update, relinearised on the device), same arrangement
 # (opened at the first update_iterated! / iterated_nis / iterated_limits)
 const libslamhip_iterated = get(ENV, "SLAMHIP_ITERATED_LIB", joinpath(@__DIR__, "libslamhip_iterated.so"))
+# the extension library of include/ext/slamhip_fej.h (first-estimates Jacobian predict, update and augment for the EKF), same
+# arrangement (opened at the first FirstEstimates / fej_limits)
+const libslamhip_fej = get(ENV, "SLAMHIP_FEJ_LIB", joinpath(@__DIR__, "libslamhip_fej.so"))
 
 const SLAM_OK = Cint(0)
 const SLAM_PF_HALTED = Cint(1)
@@ -720,6 +724,120 @@ function observe_iterated!(s::EKFSlamState, z::AbstractMatrix, R::AbstractMatrix
     res = update_iterated!(s, zf, R, idf; max_iter = max_iter, tol = tol)
     augment!(s, zn, R)
     assoc, res
+end
+
+# ---- first-estimates Jacobians (include/ext/slamhip_fej.h; no counterpart in the reference) ---------------------------------------
+"    fej_limits() -> observations per update call as libslamhip_fej.so reports them."
+function fej_limits()
+    out = zeros(Int32, 1)
+    check(ccall((:slam_ekf_fej_limits, libslamhip_fej), Cint, (Ptr{Int32},), out))
+    Int(out[1])
+end
+
+"""
+    FirstEstimates(s)   (or fej(s))
+
+The linearisation points of a first-estimates Jacobian (FEJ) filter over `s`, on the device beside the state: `lin`, the pose the
+vehicle's Jacobians are evaluated at (the predicted pose, never an updated one), and `first`, every landmark's first estimate.
+`predict!`, `update!` and `augment!` on this object are `ekf_predict!`, `ekf_update!` (Cholesky form) and `augment!` of `s` with the
+Jacobians evaluated there, so that the filter gains no information along the three unobservable directions of the map.  After the map
+was renumbered outside the object (remove_features!, merge_landmarks!, join!) it refuses to work until `remap!` was told how.
+`s` must outlive the object; `close!(f)` releases it early.
+"""
+mutable struct FirstEstimates{T<:Union{Float32,Float64}}
+    handle::Ptr{Cvoid}
+    state::EKFSlamState{T}
+    function FirstEstimates(s::EKFSlamState{T}) where {T}
+        h = Ref{Ptr{Cvoid}}(C_NULL)
+        check(ccall((:slam_ekf_fej_create, libslamhip_fej), Cint, (Ref{Ptr{Cvoid}}, Ptr{Cvoid}), h, handle(s)))
+        f = new{T}(h[], s)
+        finalizer(close!, f)
+        return f
+    end
+end
+
+fej(s::EKFSlamState) = FirstEstimates(s)
+
+function close!(f::FirstEstimates)
+    if f.handle != C_NULL
+        ccall((:slam_ekf_fej_destroy, libslamhip_fej), Cint, (Ptr{Cvoid},), f.handle)
+        f.handle = C_NULL
+    end
+    nothing
+end
+
+"    predict!(f, v, g, wheelbase, Q, dt): ekf_predict! with the vehicle Jacobian taken between lin and the new pose; lin becomes the new pose."
+function predict!(f::FirstEstimates, v::Real, g::Real, wheelbase::Real, Q::AbstractMatrix, dt::Real)
+    check(ccall((:slam_ekf_fej_predict, libslamhip_fej), Cint, (Ptr{Cvoid}, Cdouble, Cdouble, Cdouble, Ptr{Cdouble}, Cdouble),
+                f.handle, v, g, wheelbase, colmajor4(Q), dt))
+    nothing
+end
+
+"""
+    update!(f, z, R, idf) -> 4 x batches matrix of [v' inv(S) v, log det S, smallest pivot, -1]
+
+The residuals at the current mean, the Jacobians at lin and the first estimates, then the Cholesky-form update.  More than 8
+observations go as consecutive batches of 8: the Jacobians do not move between them, the residuals follow the mean.
+"""
+function update!(f::FirstEstimates, z::AbstractMatrix, R::AbstractMatrix, idf)
+    m = size(z, 2)
+    ids = Vector{Int32}(vec(collect(idf)))
+    length(ids) == m || throw(ArgumentError("idf and z disagree on the number of observations"))
+    zz, r = pairs64(z), colmajor4(R)
+    outs = zeros(Float64, 4, cld(m, 8))
+    for (b, lo) in enumerate(1:8:m)
+        hi = min(lo + 7, m)
+        out = zeros(Float64, 4)
+        check(ccall((:slam_ekf_fej_update, libslamhip_fej), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Int32}, Cint, Ptr{Cdouble}, Ptr{Cdouble}),
+                    f.handle, zz[:, lo:hi], ids[lo:hi], hi - lo + 1, r, out))
+        outs[:, b] = out
+    end
+    outs
+end
+
+"    augment!(f, z, R): augment! with the new landmarks' Jacobians taken between lin and their new means, which become their first estimates."
+function augment!(f::FirstEstimates, z::AbstractMatrix, R::AbstractMatrix)
+    size(z, 2) == 0 && return nothing
+    check(ccall((:slam_ekf_fej_augment, libslamhip_fej), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Cint, Ptr{Cdouble}),
+                f.handle, pairs64(z), size(z, 2), colmajor4(R)))
+    nothing
+end
+
+"    reset!(f; ids = nothing, pose = false): first of the landmarks ids (nothing: all) <- their current means; pose: lin <- the current pose."
+function reset!(f::FirstEstimates; ids = nothing, pose::Bool = false)
+    sel = ids === nothing ? Int32[] : collect(Int32, ids)
+    check(ccall((:slam_ekf_fej_reset, libslamhip_fej), Cint, (Ptr{Cvoid}, Ptr{Int32}, Cint, Cint),
+                f.handle, sel, ids === nothing ? -1 : length(sel), pose ? 1 : 0))
+    nothing
+end
+
+"    remap!(f, ids): after the map was renumbered outside: new landmark j takes the first estimate of old landmark ids[j], 0: its current mean."
+function remap!(f::FirstEstimates, ids::AbstractVector{<:Integer})
+    sel = collect(Int32, ids)
+    check(ccall((:slam_ekf_fej_remap, libslamhip_fej), Cint, (Ptr{Cvoid}, Ptr{Int32}, Cint), f.handle, sel, length(sel)))
+    nothing
+end
+
+"    transform!(f, tx, ty, theta): lin and every first estimate in another frame; call it beside transform!(s, tx, ty, theta)."
+function transform!(f::FirstEstimates, tx::Real, ty::Real, theta::Real)
+    check(ccall((:slam_ekf_fej_transform, libslamhip_fej), Cint, (Ptr{Cvoid}, Cdouble, Cdouble, Cdouble), f.handle, tx, ty, theta))
+    nothing
+end
+
+"    linearisation(f) -> (lin [3], first [2 x count]) as Float64 from the device."
+function linearisation(f::FirstEstimates)
+    count = Ref{Int32}(0)
+    check(ccall((:slam_ekf_fej_get, libslamhip_fej), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{Int32}), f.handle, C_NULL, C_NULL, count))
+    lin = zeros(Float64, 3); first = zeros(Float64, 2, Int(count[]))
+    check(ccall((:slam_ekf_fej_get, libslamhip_fej), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int32}), f.handle, lin, first, C_NULL))
+    lin, first
+end
+
+"    set_linearisation!(f, lin, first): write both (first: 2 x N of the state) to the device; the object's count becomes the state's."
+function set_linearisation!(f::FirstEstimates, lin::AbstractVector, first::AbstractMatrix)
+    check(ccall((:slam_ekf_fej_set, libslamhip_fej), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}),
+                f.handle, Vector{Float64}(lin), Matrix{Float64}(first)))
+    nothing
 end
 
 # ---- compressed local-area updates (include/ext/slamhip_local.h) -----------------------------------------------------------------

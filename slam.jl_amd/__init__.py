@@ -10,7 +10,7 @@ fails loudly if the HIP library has not been built: there is no CPU fallback.
 """
 from . import _lib  # noqa: F401  (raises ImportError when libslamhip.so is missing)
 from ._lib import NotPositiveDefinite, SlamHipError, device_count  # noqa: F401
-from .ekf import (CovarianceFactor, DeviceRef, EKFSlamState, IteratedResult, LocalArea, SlamState, add_features, associate, augment_,  # noqa: F401
+from .ekf import (CovarianceFactor, DeviceRef, EKFSlamState, FirstEstimates, IteratedResult, LocalArea, SlamState, add_features, associate, augment_,  # noqa: F401
                   compute_association, ekf_predict_, ekf_update_, mpi_to_pi, predict, predict_observation,
                   observe, remove_features, remove_features_, removal_maps, update,
                   find_duplicates, merge_features, merge_features_, merge_in_batches,

@@ -411,6 +411,29 @@ iterated_lib = Companion("iterated", ITERATED_SIGNATURES)
 ITERATED_LIB_PATH = iterated_lib.path
 
 
+# ---- fej: first-estimates Jacobian predict, update and augment for the EKF, opened when the first such object is made ---------------
+# Wired like iterated, and like it entered in neither table; its surface checks are made by tests/test_fej_ref_cpu.py.
+SLAM_FEJ_MAXOBS = 8
+
+#: every symbol include/ext/slamhip_fej.h declares
+FEJ_SIGNATURES = {
+    "slam_ekf_fej_create": (C.c_int, [C.POINTER(_h), _h]),
+    "slam_ekf_fej_destroy": (C.c_int, [_h]),
+    "slam_ekf_fej_predict": (C.c_int, [_h, C.c_double, C.c_double, C.c_double, _dp, C.c_double]),
+    "slam_ekf_fej_update": (C.c_int, [_h, _dp, _ip, C.c_int, _dp, _dp]),
+    "slam_ekf_fej_augment": (C.c_int, [_h, _dp, C.c_int, _dp]),
+    "slam_ekf_fej_reset": (C.c_int, [_h, _ip, C.c_int, C.c_int]),
+    "slam_ekf_fej_remap": (C.c_int, [_h, _ip, C.c_int]),
+    "slam_ekf_fej_transform": (C.c_int, [_h, C.c_double, C.c_double, C.c_double]),
+    "slam_ekf_fej_get": (C.c_int, [_h, _dp, _dp, _ip]),
+    "slam_ekf_fej_set": (C.c_int, [_h, _dp, _dp]),
+    "slam_ekf_fej_limits": (C.c_int, [_ip]),
+}
+
+fej_lib = Companion("fej", FEJ_SIGNATURES)
+FEJ_LIB_PATH = fej_lib.path
+
+
 def proposal_max_obs() -> int:
     """Observations per call of the proposal step with unknown correspondences, as the library reports it."""
     out = (C.c_int * 4)()

@@ -13,27 +13,20 @@
 // The observations travel in one small block copied into the handle's update workspace (Smat, free in the reference form); the
 // solve kernel appends the Jacobian blocks to it, so H never visits the host.  When an S is not positive definite the solve kernel
 // sets the handle's status word: the panel kernel then writes a ZERO panel and leaves x alone, and the down-date returns at once on
-// the same word.
+// the same word.  The block's layout and the panel kernel live in obs_panel.h, which ekf_fej.hip shares.
 #include <cmath>
 #include <vector>
 
 #include "common.h"
 #include "../../include/ext/slamhip_iterated.h"
 #include "device_math.h"
+#include "obs_panel.h"
 
 int launch_downdate(slam_ekf* h, int kp_total, const void* X, const void* Y, int pitch, const int32_t* dcount, int joseph, int k16,
                     const void* img);      // ekf_syrk.hip
 
 namespace {
 
-constexpr int MO = SLAM_ITERATED_MAXOBS;                   // 8 observations
-constexpr int LK = 2 * MO;                                 // 16: the panel's columns, one chunk of the down-date
-constexpr int LP = LK + 1;
-constexpr int NA = 3 + 2 * MO;                             // 19: the states H touches
-constexpr int HB = 10;                                     // one observation's Jacobian blocks: Hv (2 x 3, row-major), Hf (2 x 2)
-// the block in Smat, in doubles: z[16], R[4] (column-major), idf as int32[8], then -- written by the solve kernel -- Hv | Hf of
-// the last iteration, [8][10]
-constexpr int B_Z = 0, B_R = LK, B_IDF = B_R + 4, B_H = B_IDF + MO / 2, B_IN = B_H;      // B_H + 80 <= 32 x 32, the smallest Smat
 constexpr int OUTN = 10;
 
 // the model at the reduced iterate xs for observation o: its Jacobian blocks and r = z - zp with the bearing wrapped once
@@ -45,13 +38,6 @@ __device__ __forceinline__ void eval_model(const double* xs, const double* zs, i
     for (int q = 0; q < 4; ++q) hb[6 + q] = om.Hf[q];
     r[0] = zs[2 * o] - om.zp[0];
     r[1] = mpi_to_pi_d(zs[2 * o + 1] - om.zp[1]);
-}
-
-// row t of the reduced H (k x na) times a reduced vector u: the row's five non-zeros
-__device__ __forceinline__ double h_row_dot(const double* hbo, int o, int q, const double* u) {
-    const double* hv = hbo + 3 * q;
-    const double* hf = hbo + 6 + 2 * q;
-    return __builtin_fma(hf[1], u[4 + 2 * o], __builtin_fma(hf[0], u[3 + 2 * o], __builtin_fma(hv[2], u[2], __builtin_fma(hv[1], u[1], hv[0] * u[0]))));
 }
 
 // One workgroup of 256.  Thread (i, j) forms S[i][j] and owns that entry in the trailing updates of the factorisation; lane r of the
@@ -204,95 +190,6 @@ __global__ __launch_bounds__(256) void iterated_solve_kernel(const T* __restrict
     }
 }
 
-// One thread per row r of the PANEL (npad rows: the rows >= n are written as zero, the down-date has no row guards), one wave a
-// workgroup so that the rows are spread over the CUs.  Consecutive threads read consecutive rows of one column of a column-major
-// tile wherever (r, f) lies on or below the diagonal tiles -- the access pattern of the product update's pht_body.  A row reads
-// P[r, 0:3] once and the pair P[r, f : f + 2] once per DISTINCT landmark, every load issued before the first use.
-constexpr int PANEL_THREADS = 64;
-
-template <typename T>
-__global__ __launch_bounds__(PANEL_THREADS) void iterated_panel_kernel(T* __restrict__ x, const T* __restrict__ P, int ld, int n, int npad,
-                                                                        const double* __restrict__ blob, int m, const double* __restrict__ Cin,
-                                                                        const double* __restrict__ gin, T* __restrict__ W1, int pitchW,
-                                                                        const int32_t* __restrict__ status) {
-    constexpr int L = kTileLog2<T>;
-    __shared__ double Cs[LK * LK], gs[LK], hs[MO * HB];
-    __shared__ int fu[MO], slot[MO], nds;
-    const bool bad = status[0] != 0;                                      // (uniform)
-    if (!bad) {
-        for (int t = threadIdx.x; t < LK * LK; t += PANEL_THREADS) Cs[t] = Cin[t];
-        if (threadIdx.x < LK) gs[threadIdx.x] = gin[threadIdx.x];
-        for (int t = threadIdx.x; t < m * HB; t += PANEL_THREADS) hs[t] = blob[B_H + t];
-    }
-    if (threadIdx.x == 0) {                                               // the distinct landmarks, in the order of their first mention
-        const int32_t* __restrict__ idf = reinterpret_cast<const int32_t*>(blob + B_IDF);
-        int nd = 0;
-        for (int o = 0; o < MO; ++o) {
-            int s = 0;
-            if (o < m) {
-                const int f = 3 + 2 * (idf[o] - 1);
-                for (s = 0; s < nd && fu[s] != f; ++s) {}
-                if (s == nd) fu[nd++] = f;
-            }
-            slot[o] = s;
-        }
-        for (int s = nd; s < MO; ++s) fu[s] = fu[0];
-        nds = nd;
-    }
-    __syncthreads();
-    const int r = blockIdx.x * PANEL_THREADS + threadIdx.x;
-    if (r >= npad) return;
-    T* __restrict__ w = W1 + (size_t)r * pitchW;
-    if (bad || r >= n) {
-#pragma unroll
-        for (int c = 0; c < LK; ++c) w[c] = (T)0;
-        return;
-    }
-    const int nd = nds;
-    const T t0 = P[p_off(ld, L, r, 0)], t1 = P[p_off(ld, L, r, 1)], t2 = P[p_off(ld, L, r, 2)];
-    T q0[MO], q1[MO];
-#pragma unroll
-    for (int s = 0; s < MO; ++s) {
-        q0[s] = (T)0;
-        q1[s] = (T)0;
-        if (s < nd) {
-            q0[s] = sym_at(P, ld, L, r, fu[s]);                           // P[r, f]: from row f where (r, f) lies above the diagonal tiles
-            q1[s] = sym_at(P, ld, L, r, fu[s] + 1);
-        }
-    }
-    const double xr = (double)x[r];
-    const double p0 = (double)t0, p1 = (double)t1, p2 = (double)t2;
-    double dxr = 0.0, acc[LK];
-#pragma unroll
-    for (int c = 0; c < LK; ++c) acc[c] = 0.0;
-#pragma unroll
-    for (int o = 0; o < MO; ++o) {
-        if (o < m) {
-            const int s = slot[o];
-            T a0 = q0[0], a1 = q1[0];
-#pragma unroll
-            for (int u = 1; u < MO; ++u) {                                // the landmark's pair, by selects: the registers stay registers
-                a0 = s == u ? q0[u] : a0;
-                a1 = s == u ? q1[u] : a1;
-            }
-            const double* hbo = hs + o * HB;
-#pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                const double* hv = hbo + 3 * q;
-                const double* hf = hbo + 6 + 2 * q;
-                const double pht = __builtin_fma(hf[1], (double)a1, __builtin_fma(hf[0], (double)a0,
-                                   __builtin_fma(hv[2], p2, __builtin_fma(hv[1], p1, hv[0] * p0))));
-                const int row = 2 * o + q;
-#pragma unroll
-                for (int c = 0; c < LK; ++c) acc[c] += pht * Cs[row * LK + c];      // C is upper: zero below the diagonal
-                dxr += pht * gs[row];
-            }
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < LK; ++c) w[c] = (T)acc[c];
-    x[r] = (T)(xr + dxr);
-}
 
 // every rule of the header; fills the block.  h is dereferenced only after the rules that need no state
 int check_arguments(slam_ekf* h, const double* zf, const int32_t* idf, int m, const double* R, int max_iter, double tol, const double* out,

@@ -37,7 +37,7 @@ __all__ = [
     "find_duplicates", "merge_features", "merge_features_", "merge_in_batches",
     "chi2_table", "associate_joint", "observe_joint",
     "copy_state", "select_features", "select_map", "grown_capacity",
-    "CovarianceFactor", "linear_rows", "LocalArea", "IteratedResult",
+    "CovarianceFactor", "linear_rows", "LocalArea", "IteratedResult", "FirstEstimates",
 ]
 
 _DTYPES = {"f32": (SLAM_F32, np.float32), "f64": (SLAM_F64, np.float64),
@@ -355,6 +355,8 @@ class EKFSlamState(SlamState):
 
     # -- lifetime ----------------------------------------------------------------
     def close(self):
+        for obj in list(getattr(self, "_fej", ())):                       # they borrow the handle: they go first
+            obj.close()
         if getattr(self, "_jc", None):
             _lib.jc_lib().slam_ekf_jc_destroy(self._jc)               # the search workspace borrows the handle: it goes first
             self._jc = None
@@ -507,6 +509,9 @@ class EKFSlamState(SlamState):
         if max_landmarks <= self.capacity:
             return
         code = _DTYPES[self.np_dtype][0]
+        moved = [(obj, obj.get()) for obj in getattr(self, "_fej", ())]   # FirstEstimates objects follow the state: get ...
+        if any(count != self.N for _obj, (_lin, _first, count) in moved):
+            raise ValueError("a FirstEstimates object does not follow the map (remap it) and cannot move into a larger handle")
         new = C.c_void_p()
         check(lib.slam_ekf_create(C.byref(new), code, max_landmarks, self.device))
         try:
@@ -521,9 +526,14 @@ class EKFSlamState(SlamState):
         if getattr(self, "_jc", None):
             _lib.jc_lib().slam_ekf_jc_destroy(self._jc)               # it borrows the old handle
             self._jc = None
+        for obj, _saved in moved:
+            obj._release()                                                # (it borrows the old handle)
         old, self._h = self._h, new
         self.max_landmarks = max_landmarks
         lib.slam_ekf_destroy(old)                                     # (waits for the copy's last read of it)
+        for obj, (lin, first, _count) in moved:                           # ... / set, on the new handle
+            obj._attach()
+            obj.set(lin, first)
 
     def _grow_for(self, needed):
         self.reserve(grown_capacity(self.capacity, needed))
@@ -860,6 +870,13 @@ class EKFSlamState(SlamState):
         res = self.update_iterated(z[:, assoc > 0], R, assoc[assoc > 0], max_iter=max_iter, tol=tol)
         self.add_features(z[:, assoc < 0], R)
         return assoc, res
+
+    # -- first-estimates Jacobians (libslamhip_fej.so, include/ext/slamhip_fej.h) -----------------------------------------
+    def fej(self):
+        """A :class:`FirstEstimates` object attached to this state: predict, update and add_features whose Jacobians are evaluated
+        at every landmark's first estimate and at the vehicle's predicted pose, so that the filter gains no information along the
+        three unobservable directions of the map.  It starts from the current estimates and is closed with the state."""
+        return FirstEstimates(self)
 
     def transform(self, tx, ty, theta):
         """Express the whole state in another frame, in place on the device (slam_ekf_transform): every position becomes
@@ -1206,6 +1223,137 @@ class CovarianceFactor:
         count)) from the caller's ``numpy.random.Generator``, so the draw is the caller's to reproduce."""
         Z = rng.standard_normal((self.n, int(count)))
         return self.mean()[:, None] + self.colour(Z)
+
+
+class FirstEstimates:
+    """The linearisation points of a first-estimates Jacobian (FEJ) filter over ``state`` (include/ext/slamhip_fej.h), on the device
+    beside the state: ``lin``, the pose the vehicle's Jacobians are evaluated at (the predicted pose, never an updated one), and
+    ``first``, every landmark's first estimate.  :meth:`predict`, :meth:`update` and :meth:`add_features` are the state's own with
+    the Jacobians evaluated there; no formula changes.  While the object is in use, move the state through it: a call of the
+    state's own predict / update leaves ``lin`` behind (:meth:`reset` re-anchors it), and after the map was renumbered
+    (remove_landmarks, merge_landmarks, select_from, join) the object refuses to work until :meth:`remap` was told how.  With
+    ``grow=True`` on the state the object follows it into a larger handle."""
+
+    def __init__(self, state):
+        if not isinstance(state, EKFSlamState):
+            raise TypeError("FirstEstimates needs an EKFSlamState")
+        self._lib = _lib.fej_lib()
+        self.state = state
+        self._f = C.c_void_p()
+        self._attach()
+        if getattr(state, "_fej", None) is None:
+            state._fej = []
+        state._fej.append(self)
+
+    def _attach(self):
+        check(self._lib.slam_ekf_fej_create(C.byref(self._f), self.state._h))
+
+    def _release(self):
+        if getattr(self, "_f", None) is not None and self._f:
+            self._lib.slam_ekf_fej_destroy(self._f)
+            self._f = C.c_void_p()
+
+    # -- lifetime ----------------------------------------------------------------
+    def close(self):
+        self._release()
+        held = getattr(getattr(self, "state", None), "_fej", None)
+        if held and self in held:
+            held.remove(self)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # -- the linearisation points ---------------------------------------------------
+    def get(self):
+        """``(lin [3], first [2 count], count)`` as float64 from the device (slam_ekf_fej_get); first holds (x, y) pairs in landmark
+        order, like x[3:]."""
+        count = C.c_int32()
+        check(self._lib.slam_ekf_fej_get(self._f, None, None, C.byref(count)))
+        lin, first = np.zeros(3), np.zeros(2 * count.value)
+        check(self._lib.slam_ekf_fej_get(self._f, _ptr(lin), _ptr(first) if count.value else None, None))
+        return lin, first, count.value
+
+    def set(self, lin=None, first=None):
+        """Write ``lin`` (3 values) and / or ``first`` (2 state.N values) to the device (slam_ekf_fej_set): a checkpoint restored,
+        or designed linearisation points.  With ``first`` the object's count becomes the state's."""
+        a = None if lin is None else _dbl(lin, 3)
+        b = None if first is None else _dbl(np.asarray(first, dtype=np.float64).reshape(-1), 2 * self.state.N)
+        if b is not None and not b.size:
+            b = np.zeros(1)                                               # an empty map: a pointer that is not null, nothing is read
+        check(self._lib.slam_ekf_fej_set(self._f, _ptr(a) if a is not None else None, _ptr(b) if b is not None else None))
+
+    def reset(self, ids=None, pose=False):
+        """``first`` of the landmarks ``ids`` (1-based; None: all) becomes their current mean, and with ``pose`` ``lin`` becomes
+        the current pose (slam_ekf_fej_reset): the linearisation points re-anchored, e.g. after a loop was closed."""
+        if ids is None:
+            check(self._lib.slam_ekf_fej_reset(self._f, None, -1, 1 if pose else 0))
+            return
+        ids = np.ascontiguousarray(np.asarray(ids, dtype=np.int32).reshape(-1))
+        check(self._lib.slam_ekf_fej_reset(self._f, _ptr(ids, C.c_int32) if ids.size else None, int(ids.size), 1 if pose else 0))
+
+    def remap(self, ids):
+        """After the map was renumbered outside the object: new landmark j takes the first estimate of old landmark ``ids[j - 1]``
+        (1-based), or its current mean where ``ids[j - 1]`` is 0 (slam_ekf_fej_remap).  One entry per landmark of the state.  For
+        ``new_index = state.remove_landmarks(gone)`` the map is ``np.flatnonzero(new_index) + 1``."""
+        ids = np.ascontiguousarray(np.asarray(ids, dtype=np.int32).reshape(-1))
+        check(self._lib.slam_ekf_fej_remap(self._f, _ptr(ids, C.c_int32) if ids.size else None, int(ids.size)))
+
+    def transform(self, tx, ty, theta):
+        """``lin`` and every first estimate expressed in another frame (slam_ekf_fej_transform): call it beside
+        ``state.transform(tx, ty, theta)``, which this does NOT do."""
+        check(self._lib.slam_ekf_fej_transform(self._f, float(tx), float(ty), float(theta)))
+
+    # -- the steps --------------------------------------------------------------------
+    def predict(self, v, g, wheelbase, Q, dt):
+        """``state.predict`` with the vehicle Jacobian taken between ``lin`` and the new pose; ``lin`` becomes the new pose.
+        Enqueued."""
+        q = _small(Q)
+        check(self._lib.slam_ekf_fej_predict(self._f, float(v), float(g), float(wheelbase), _ptr(q), float(dt)))
+
+    def update(self, zf, R, idf):
+        """``state.update`` (Cholesky form) with the residuals at the current mean and the Jacobians at ``lin`` and the first
+        estimates (slam_ekf_fej_update).  More than 8 observations go as consecutive batches of 8 in the order given: the Jacobians do
+        not move between the batches, the residuals of a batch are taken at the mean the batch before left.  Returns one row
+        ``[v' inv(S) v, log det S, smallest pivot, -1]`` per batch (None without an observation); raises NotPositiveDefinite with the
+        state unchanged by the failing batch."""
+        zp = _obs(zf)
+        ids = np.ascontiguousarray(np.asarray(idf, dtype=np.int32).reshape(-1))
+        if ids.shape[0] != zp.shape[0]:
+            raise ValueError("idf and z disagree on the number of observations")
+        if zp.shape[0] == 0:
+            return None
+        r = _small(R)
+        B = _lib.SLAM_FEJ_MAXOBS
+        outs = np.zeros(((zp.shape[0] + B - 1) // B, 4))
+        for b, s in enumerate(range(0, zp.shape[0], B)):
+            zb, ib = np.ascontiguousarray(zp[s:s + B]), np.ascontiguousarray(ids[s:s + B])
+            check(self._lib.slam_ekf_fej_update(self._f, _ptr(zb), _ptr(ib, C.c_int32), zb.shape[0], _ptr(r), _ptr(outs[b])))
+        return outs
+
+    def add_features(self, zn, R):
+        """``state.add_features`` with the new landmarks' Jacobians taken between ``lin`` and their new means, which become their
+        first estimates (slam_ekf_fej_augment).  With ``grow=True`` on the state both move into a larger handle when needed."""
+        zp = _obs(zn)
+        if zp.shape[0] == 0:
+            return
+        r = _small(R)
+        rc = self._lib.slam_ekf_fej_augment(self._f, _ptr(zp), zp.shape[0], _ptr(r))
+        if rc == _lib.SLAM_E_CAPACITY and self.state.grow:               # decided before anything was enqueued: grow, then again
+            self.state._grow_for(self.state.N + zp.shape[0])
+            rc = self._lib.slam_ekf_fej_augment(self._f, _ptr(zp), zp.shape[0], _ptr(r))
+        check(rc)
+
+    def observe(self, z, R, gate1, gate2):
+        """The product's association at the current estimates (``state.associate_vector``), then this update and this
+        add_features.  Returns the association vector."""
+        z = np.asarray(z, dtype=np.float64).reshape(2, -1)
+        assoc = self.state.associate_vector(z, R, gate1, gate2)
+        self.update(z[:, assoc > 0], R, assoc[assoc > 0])
+        self.add_features(z[:, assoc < 0], R)
+        return assoc
 
 
 class LocalArea:

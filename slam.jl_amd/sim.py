@@ -172,7 +172,7 @@ def default_QR():
 def sim(filt, waypoints: np.ndarray, landmarks: np.ndarray, seed: int, nlaps: int = 2,
         max_steps: int = 100000, monitor=None, fused: bool = False, prune_after=None, merge_gate=None,
         submap_steps=None, association: str = "nearest", nees_every=None, fix_every: int = 0,
-        fix_sigma: float = 0.5, local_radius=None, iterated=None) -> SimLog:
+        fix_sigma: float = 0.5, local_radius=None, iterated=None, fej: bool = False) -> SimLog:
     """The loop of sim/ekfslam-sim.jl:80-141 without sleep/pause.
 
     ``filt`` must already hold the initial state (x = initial pose, P = 0).
@@ -218,7 +218,14 @@ def sim(filt, waypoints: np.ndarray, landmarks: np.ndarray, seed: int, nlaps: in
     every observation step is ``filt.update_iterated(zf, R, idf, max_iter=k)`` -- relinearised up to k times, more than 8 matched
     observations in consecutive batches of 8 -- after the nearest-neighbour association; with ``fused`` the three calls are
     ``filt.observe_iterated``.  Not available with joint association, ``submap_steps`` or ``local_radius``.
+    ``fej``: False (default) changes nothing.  True (first-estimates Jacobians, no counterpart in the reference): predict, update and
+    add_features go through ``filt.fej()`` -- the Jacobians evaluated at every landmark's first estimate and at the predicted pose,
+    the association at the current estimates as before; with ``fused`` the observation step is that object's ``observe`` (joint
+    association: the three calls, fused or not).  Not available with ``submap_steps``, ``local_radius``, ``iterated``, ``prune_after`` or ``merge_gate``.
     """
+    if fej and (submap_steps is not None or local_radius is not None or iterated is not None or prune_after is not None
+                or merge_gate is not None):
+        raise ValueError("fej is not available with submap_steps, local_radius, iterated, prune_after or merge_gate")
     if iterated is not None:
         iterated = int(iterated)
         if iterated < 1 or association != "nearest" or submap_steps is not None or local_radius is not None:
@@ -254,6 +261,7 @@ def sim(filt, waypoints: np.ndarray, landmarks: np.ndarray, seed: int, nlaps: in
     born = np.zeros(0, dtype=np.int64)      # prune_after: observation step that created landmark j (at [j - 1]) ...
     hits = np.zeros(0, dtype=np.int64)      # ... and its matches since
     tags = np.zeros(0, dtype=np.int64)      # nees_every: the true landmark (1-based) whose observation created landmark j
+    step = filt.fej() if fej else filt      # what takes predict / update / add_features / observe; everything else goes to filt
     while vehicle.waypoint_id != 0 and nsteps < max_steps:
         steer(vehicle, waypoints, D_MIN, DT)                              # :85
         if vehicle.waypoint_id == 0 and nlaps > 1:                        # :88-91
@@ -262,17 +270,17 @@ def sim(filt, waypoints: np.ndarray, landmarks: np.ndarray, seed: int, nlaps: in
         step_vehicle(vehicle, DT)                                         # :94
         vehicle.measured_speed = vehicle.target_speed + rng.standard_normal() * math.sqrt(Q[0, 0])
         vehicle.measured_gamma = vehicle.target_gamma + rng.standard_normal() * math.sqrt(Q[1, 1])
-        filt.predict(vehicle.measured_speed, vehicle.measured_gamma, vehicle.wheelbase, Q, DT)  # :100
+        step.predict(vehicle.measured_speed, vehicle.measured_gamma, vehicle.wheelbase, Q, DT)  # :100
         log.controls.append((vehicle.measured_speed, vehicle.measured_gamma))
         dtsum += DT                                                       # :102
         if dtsum > DT_OBS:                                                # :105 (fires every 9th step)
             dtsum = 0.0
             z, ztags = get_observations(vehicle, landmarks, R, rng)       # :108
-            if fused:
+            if fused and not (fej and joint):
                 if iterated is not None:
                     assoc = np.asarray(filt.observe_iterated(z, R, GATE1, GATE2, max_iter=iterated)[0])
                 else:
-                    assoc = np.asarray(filt.observe_joint(z, R, GATE1, GATE2)[0] if joint else filt.observe(z, R, GATE1, GATE2))   # :114-120 in one call
+                    assoc = np.asarray(filt.observe_joint(z, R, GATE1, GATE2)[0] if joint else step.observe(z, R, GATE1, GATE2))   # :114-120 in one call
                 idf = assoc[assoc > 0]
                 zn = np.asarray(z, dtype=float).reshape(2, -1)[:, assoc < 0]
             else:
@@ -280,8 +288,8 @@ def sim(filt, waypoints: np.ndarray, landmarks: np.ndarray, seed: int, nlaps: in
                 if iterated is not None:
                     filt.update_iterated(zf, R, idf, max_iter=iterated)
                 else:
-                    filt.update(zf, R, idf)                               # :117
-                filt.add_features(zn, R)                                  # :120
+                    step.update(zf, R, idf)                               # :117
+                step.add_features(zn, R)                                  # :120
             log.obs_steps.append(nsteps)
             log.observations.append(np.array(z))
             log.assoc.append((np.asarray(idf).reshape(-1).tolist(), int(np.asarray(zn).reshape(2, -1).shape[1])))
@@ -331,6 +339,8 @@ def sim(filt, waypoints: np.ndarray, landmarks: np.ndarray, seed: int, nlaps: in
             log.nees_truth.append(x_true)
         if monitor is not None:
             monitor(vehicle, filt, nsteps)
+    if fej:
+        step.close()
     if nees_every is not None:
         log.landmark_tags = tags
     if getattr(filt, "path_history", None) is not None:                   # a PFSlamState that tracks its path (FastSLAM.track_path)
