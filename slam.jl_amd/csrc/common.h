@@ -266,5 +266,17 @@ int ensure_pmax(slam_ekf* h);       // the pre-gate's variance bound is current
 int launch_nis(slam_ekf* h, const double z1[2], int j, const double R[4]);
 int launch_obs_model(slam_ekf* h, int j);
 int launch_update(slam_ekf* h, int m, const double R[4], int form, bool device_count);   // device_count: m is an upper bound, kernels read d_count[0]
+int launch_downdate(slam_ekf* h, int kp_total, const void* X, const void* Y, int pitch, const int32_t* dcount, int joseph, int k16,
+                    const void* img);      // P -= X Y' on the panels' kp_total columns (ekf_syrk.hip)
 int ensure_update_workspace(slam_ekf* h, int m);
 int ensure_obs_capacity(slam_ekf* h, int nobs);
+
+// The tail of a small update's call (ekf_linear.hip, ekf_iterated.hip, ekf_fej.hip): the outn doubles its front half left in
+// d_small copied back into out, the stream synchronised.  SLAM_E_NOTPD when out[ifail] names a failing pivot: the caller words
+// the message.
+static inline int slam_small_out(slam_ekf* h, double* out, int outn, int ifail) {
+    HIP_TRY(hipMemcpyAsync(h->h_small, h->d_small, sizeof(double) * outn, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    for (int q = 0; q < outn; ++q) out[q] = h->h_small[q];
+    return out[ifail] >= 0.0 ? SLAM_E_NOTPD : SLAM_OK;
+}

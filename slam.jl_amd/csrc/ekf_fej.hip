@@ -7,9 +7,10 @@
 //     fej_strip_kernel    predict: one launch over the vehicle's three columns of the tile-major matrix, as predict_kernel
 //                         (ekf_strip.hip) walks them.  Every workgroup forms x+ and Gv for itself from the stored pose and lin; the
 //                         workgroup that arrives last -- after every workgroup has read both -- rewrites P_vv, the pose and lin
+//                         (strip_tail.h)
 //     fej_front_kernel    update, one workgroup: gathers P[a, a] (at most 19 x 19), x[a], lin and first[a] into LDS, takes the
-//                         residuals at x and the Jacobian blocks at (lin, first), forms S, its factor, C = inv(chol(S)), g and
-//                         `out`, and leaves the Jacobian blocks in the observation block for the panel
+//                         residuals at x and the Jacobian blocks at (lin, first), forms S (obs_panel.h), its factor,
+//                         C = inv(chol(S)), g and `out` (small_front.h), and leaves the Jacobian blocks in the observation block
 //     iterated_panel_kernel (obs_panel.h)   PHt rows, W1 and x += PHt g from those blocks; a zero panel when the status word is set
 //     launch_downdate     P -= W1 W1' on the plain 16-column panel (ekf_syrk.hip), which also keeps Pside
 //     fej_augment_kernel  augment: augment_kernel (ekf_strip.hip) with Gv = [I | J (lm - lin_xy)], and first <- lm
@@ -23,9 +24,7 @@
 #include "../../include/ext/slamhip_fej.h"
 #include "device_math.h"
 #include "obs_panel.h"
-
-int launch_downdate(slam_ekf* h, int kp_total, const void* X, const void* Y, int pitch, const int32_t* dcount, int joseph, int k16,
-                    const void* img);      // ekf_syrk.hip
+#include "strip_tail.h"
 
 struct slam_ekf_fej {
     slam_ekf* h;
@@ -44,8 +43,7 @@ static_assert(SLAM_FEJ_MAXOBS == MO, "the panel kernel takes 8 observations");
 // ---- predict -----------------------------------------------------------------------------------------------------------------------
 // As predict_kernel: thread f >= 3 owns row f of the column strip and its mirror.  x+ is rounded to T BEFORE Gv is formed from it,
 // so that Gv carries the old linearisation pose exactly onto the new one (lin <- x+ as stored).  The pose and lin are read by every
-// workgroup and rewritten by the one that arrives last at the counter; the strip and the pose block are disjoint, so the arrival is
-// a relaxed atomic without fences (ekf_strip.hip).
+// workgroup and rewritten by the one that arrives last at the counter (strip_tail.h).
 template <typename T>
 __global__ __launch_bounds__(256) void fej_strip_kernel(T* __restrict__ x, T* __restrict__ P, int ld, int n, double* __restrict__ lin,
                                                          double v, double g, double w, double Q0, double Q1, double Q2, double Q3,
@@ -65,30 +63,13 @@ __global__ __launch_bounds__(256) void fej_strip_kernel(T* __restrict__ x, T* __
         p_store_sym(P, ld, tlog, f, 1, (T)(p1 + gb * p2));
         p_store_sym(P, ld, tlog, f, 2, (T)p2);
     }
-    __shared__ int last;
-    __syncthreads();                         // every thread of the workgroup has the pose and lin
-    if (threadIdx.x == 0)
-        last = __hip_atomic_fetch_add(arrive, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (int)gridDim.x - 1;
-    __syncthreads();
-    if (!last || threadIdx.x != 0) return;
-    __hip_atomic_store(arrive, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);          // re-armed
+    if (!strip_arrive_last(arrive) || threadIdx.x != 0) return;
+    strip_rearm(arrive);
     const double Gv[3][3] = {{1.0, 0.0, ga}, {0.0, 1.0, gb}, {0.0, 0.0, 1.0}};
     const double Gu[3][2] = {{dt * cs, -vts}, {dt * sn, vtc}, {dt * sin(g) / w, v * dt * cos(g) / w}};
-    const double Q[2][2] = {{Q0, Q2}, {Q1, Q3}};   // column-major input
-    double Pvv[3][3], GP[3][3], GQ[3][2];
-    for (int r = 0; r < 3; ++r)
-        for (int c = 0; c < 3; ++c) Pvv[r][c] = (double)P[p_off(ld, tlog, r, c)];
-    for (int r = 0; r < 3; ++r)
-        for (int c = 0; c < 3; ++c) GP[r][c] = Gv[r][0] * Pvv[0][c] + Gv[r][1] * Pvv[1][c] + Gv[r][2] * Pvv[2][c];
-    for (int r = 0; r < 3; ++r)
-        for (int c = 0; c < 2; ++c) GQ[r][c] = Gu[r][0] * Q[0][c] + Gu[r][1] * Q[1][c];
-    // the lower triangle, each entry formed once and mirrored: (r, c) and (c, r) formed separately round differently
-    for (int r = 0; r < 3; ++r)
-        for (int c = 0; c <= r; ++c) {
-            const T val = (T)((GP[r][0] * Gv[c][0] + GP[r][1] * Gv[c][1] + GP[r][2] * Gv[c][2]) + (GQ[r][0] * Gu[c][0] + GQ[r][1] * Gu[c][1]));
-            P[p_off(ld, tlog, r, c)] = val;
-            P[p_off(ld, tlog, c, r)] = val;
-        }
+    double GQG[3][3];
+    strip_gu_q_gut(Gu, Q0, Q1, Q2, Q3, GQG);
+    strip_rewrite_pvv(P, ld, tlog, Gv, GQG);
     x[0] = xp0;
     x[1] = xp1;
     x[2] = xp2;
@@ -98,32 +79,19 @@ __global__ __launch_bounds__(256) void fej_strip_kernel(T* __restrict__ x, T* __
 }
 
 // ---- update: the front half ----------------------------------------------------------------------------------------------------------
-// One workgroup of 256, the shape of iterated_solve_kernel for its one iteration: thread (i, j) forms S[i][j] and owns that entry in
-// the trailing updates of the factorisation; rows / columns >= k are the identity, so the chain of pivots stops at k.  Every
-// decision is taken from values all threads read from LDS, so it is uniform.
+// One workgroup of 256: the two model evaluations between the pieces of obs_panel.h and small_front.h.
 template <typename T>
 __global__ __launch_bounds__(256) void fej_front_kernel(const T* __restrict__ x, const T* __restrict__ P, int ld, double* __restrict__ blob,
                                                          int m, const double* __restrict__ lin, const double* __restrict__ first,
                                                          double* __restrict__ Cout, double* __restrict__ gout, double* __restrict__ out4,
                                                          int32_t* __restrict__ status) {
-    constexpr int L = kTileLog2<T>;
     __shared__ double Pa[NA][NA + 1], PaHt[NA][LP], M[LK][LP], Li[LK][LP];
     __shared__ double xa[NA], la[NA], v[LK], y[LK], hb[MO][HB], zs[LK], Rs[4];
     __shared__ int cols[NA];
     const int tid = threadIdx.x, k = 2 * m, na = 3 + 2 * m;
-    const int32_t* __restrict__ idf = reinterpret_cast<const int32_t*>(blob + B_IDF);
-    if (tid < NA) cols[tid] = tid < 3 ? tid : (tid < na ? 3 + 2 * (idf[(tid - 3) >> 1] - 1) + ((tid - 3) & 1) : 0);
-    if (tid < LK) zs[tid] = tid < k ? blob[B_Z + tid] : 0.0;
-    if (tid < 4) Rs[tid] = blob[B_R + tid];
-    __syncthreads();
-    for (int t = tid; t < na * na; t += 256) {
-        const int r = t / na, c = t - r * na;
-        Pa[r][c] = (double)sym_at(P, ld, L, cols[r], cols[c]);
-    }
-    if (tid < na) {
-        xa[tid] = (double)x[cols[tid]];
-        la[tid] = tid < 3 ? lin[tid] : first[cols[tid] - 3];
-    }
+    obs_tables(blob, m, cols, zs, Rs);
+    obs_gather(x, P, ld, cols, na, Pa, xa);
+    if (tid < na) la[tid] = tid < 3 ? lin[tid] : first[cols[tid] - 3];
     __syncthreads();
     if (tid < m) {            // the residual at the stored mean, the Jacobian blocks at the linearisation points
         const ObsModel om = obs_model(xa[0], xa[1], xa[2], xa[3 + 2 * tid], xa[4 + 2 * tid]);
@@ -136,43 +104,12 @@ __global__ __launch_bounds__(256) void fej_front_kernel(const T* __restrict__ x,
         for (int q = 0; q < 4; ++q) hb[tid][6 + q] = ol.Hf[q];
     }
     __syncthreads();
-    for (int t = tid; t < na * LK; t += 256) {                              // P[a, a] H'
-        const int r = t >> 4, c = t & 15;
-        PaHt[r][c] = c < k ? h_row_dot(hb[c >> 1], c >> 1, c & 1, Pa[r]) : 0.0;
-    }
+    obs_paht(hb, Pa, PaHt, k, na);
     __syncthreads();
-    const int i = tid >> 4, j = tid & 15;
-    {
-        double s = i == j ? 1.0 : 0.0;
-        if (i < k && j < k) {
-            const int o = i >> 1, q = i & 1;
-            const double* hv = hb[o] + 3 * q;
-            const double* hf = hb[o] + 6 + 2 * q;
-            s = __builtin_fma(hf[1], PaHt[4 + 2 * o][j], __builtin_fma(hf[0], PaHt[3 + 2 * o][j],
-                __builtin_fma(hv[2], PaHt[2][j], __builtin_fma(hv[1], PaHt[1][j], hv[0] * PaHt[0][j]))));
-            if ((i >> 1) == (j >> 1)) s += Rs[(j & 1) * 2 + (i & 1)];
-        }
-        M[i][j] = s;
-    }
-    __syncthreads();
-    const double sym = (M[i][j] + M[j][i]) * 0.5;                         // S = (S + S') / 2
-    __syncthreads();
-    M[i][j] = sym;
-    __syncthreads();
-    // right-looking Cholesky S = L L'; every thread reads the same pivot
-    int fail = -1;
-    double piv = 0.0, lmin = INFINITY;
-    for (int c = 0; c < k; ++c) {
-        piv = M[c][c];
-        if (!(piv > 0.0) || !(piv < INFINITY)) { fail = c; break; }
-        const double d = sqrt(piv);
-        lmin = d < lmin ? d : lmin;
-        __syncthreads();
-        if (tid >= c && tid < LK) M[tid][c] = M[tid][c] / d;
-        __syncthreads();
-        if (i > c && j > c && j <= i) M[i][j] -= M[i][c] * M[j][c];
-        __syncthreads();
-    }
+    M[tid >> 4][tid & 15] = obs_s_entry(hb, PaHt, Rs, k, tid >> 4, tid & 15);
+    small_symmetrise(M);
+    double piv = 0.0, lmin;
+    const int fail = small_cholesky(M, k, piv, lmin, nullptr);
     if (fail >= 0) {
         if (tid == 0) {
             out4[0] = 0.0; out4[1] = 0.0; out4[2] = piv; out4[3] = (double)fail;
@@ -180,26 +117,9 @@ __global__ __launch_bounds__(256) void fej_front_kernel(const T* __restrict__ x,
         }
         return;
     }
-    if (tid < k) {       // inv(L): lane c solves L X[:, c] = e_c
-        for (int r = 0; r < k; ++r) {
-            double s = r == tid ? 1.0 : 0.0;
-            for (int q = tid; q < r; ++q) s -= M[r][q] * Li[q][tid];
-            Li[r][tid] = r < tid ? 0.0 : s / M[r][r];
-        }
-    }
-    __syncthreads();
-    if (tid < k) {       // y = C' v = inv(L) v
-        double s = 0.0;
-        for (int q = 0; q <= tid; ++q) s += Li[tid][q] * v[q];
-        y[tid] = s;
-    }
-    __syncthreads();
-    if (tid < LK) {      // g = C y = inv(L)' y
-        double s = 0.0;
-        for (int q = tid; q < k; ++q) s += Li[q][tid] * y[q];
-        gout[tid] = s;                                                    // (no term for tid >= k)
-    }
-    Cout[tid] = (i < k && j < k && i <= j) ? Li[j][i] : 0.0;            // C[i][j] = inv(L)[j][i], zero outside the leading k x k
+    const double gl = small_solve(M, Li, v, y, k);
+    if (tid < LK) gout[tid] = gl;
+    small_store_c(Li, k, Cout);
     if (tid < m * HB) blob[B_H + tid] = hb[tid / HB][tid % HB];          // the Jacobian blocks, for the panel
     if (tid == 0) {
         double nis = 0.0, lsum = 0.0;
@@ -335,13 +255,6 @@ __global__ __launch_bounds__(256) void fej_transform_kernel(double* __restrict__
     if (t == 0) lin[2] = mpi_to_pi_d(lin[2] + theta);
 }
 
-int check_R(const double* R) {
-    ARG_CHECK(slam_all_finite(R, 4), "R is not finite");
-    ARG_CHECK(R[1] == R[2], "R is not symmetric");
-    ARG_CHECK(R[0] > 0.0 && R[0] * R[3] - R[1] * R[2] > 0.0, "R is not positive definite");
-    return SLAM_OK;
-}
-
 #define FEJ_SAME_MAP(f) ARG_CHECK((f)->N == (f)->h->N, "the map changed outside the object (its landmark count differs from the state's): call slam_ekf_fej_remap")
 
 int take(slam_ekf_fej* f, const int32_t* ids_dev, int cnt, int pose) {
@@ -366,22 +279,13 @@ void release(slam_ekf_fej* f) {
 template <typename T>
 int enqueue_update(slam_ekf_fej* f, int m) {
     slam_ekf* h = f->h;
-    const int n = 3 + 2 * h->N;
-    double* blob = h->Smat;
     {
         KTimer t(h, SLAM_K_FACTOR);
-        hipLaunchKernelGGL(fej_front_kernel<T>, dim3(1), dim3(256), 0, h->stream, (const T*)h->x, (const T*)h->P, h->ld, blob, m,
+        hipLaunchKernelGGL(fej_front_kernel<T>, dim3(1), dim3(256), 0, h->stream, (const T*)h->x, (const T*)h->P, h->ld, h->Smat, m,
                            (const double*)f->lin, (const double*)f->first, h->Cmat, h->gvec, h->d_small, h->d_status);
     }
     HIP_TRY(hipGetLastError());
-    {
-        KTimer t(h, SLAM_K_W1);
-        hipLaunchKernelGGL(iterated_panel_kernel<T>, dim3((h->npad + PANEL_THREADS - 1) / PANEL_THREADS), dim3(PANEL_THREADS), 0, h->stream,
-                           (T*)h->x, (const T*)h->P, h->ld, n, h->npad, (const double*)blob, m, (const double*)h->Cmat,
-                           (const double*)h->gvec, (T*)h->W1, 2 * h->kcap, (const int32_t*)h->d_status);
-    }
-    HIP_TRY(hipGetLastError());
-    return launch_downdate(h, LK, h->W1, h->W1, 2 * h->kcap, (const int32_t*)nullptr, 0, LK, nullptr);
+    return enqueue_obs_panel<T>(h, m);
 }
 
 }  // namespace
@@ -457,16 +361,8 @@ extern "C" int slam_ekf_fej_update(slam_ekf_fej_t f, const double* zf, const int
     if ((rc = check_R(R))) return rc;
     FEJ_SAME_MAP(f);
     slam_ekf* h = f->h;
-    std::vector<double> blob(B_IN, 0.0);
-    int32_t* words = reinterpret_cast<int32_t*>(blob.data() + B_IDF);
-    for (int o = 0; o < MO; ++o) words[o] = 1;
-    for (int o = 0; o < m; ++o) {
-        ARG_CHECK(idf[o] >= 1 && idf[o] <= h->N, "idf entry out of range (Julia: BoundsError)");
-        words[o] = idf[o];
-        blob[B_Z + 2 * o] = zf[2 * o];
-        blob[B_Z + 2 * o + 1] = zf[2 * o + 1];
-    }
-    for (int q = 0; q < 4; ++q) blob[B_R + q] = R[q];
+    std::vector<double> blob;
+    if ((rc = obs_block_fill(h, zf, idf, m, R, blob))) return rc;
     HIP_TRY(hipSetDevice(h->device));
     if ((rc = ensure_update_workspace(h, MO))) return rc;                 // kcap >= 32: Smat holds the block, W1 16 columns
     SlamDrainOnExit drain{h->stream};
@@ -474,14 +370,9 @@ extern "C" int slam_ekf_fej_update(slam_ekf_fej_t f, const double* zf, const int
     rc = h->dtype == SLAM_F32 ? enqueue_update<float>(f, m) : enqueue_update<double>(f, m);
     if (rc) return rc;
     h->grid_force = 1;                                                    // the means moved: the grid is rebuilt at the next query
-    HIP_TRY(hipMemcpyAsync(h->h_small, h->d_small, sizeof(double) * 4, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    for (int q = 0; q < 4; ++q) out[q] = h->h_small[q];
-    if (out[3] >= 0.0) {
+    if ((rc = slam_small_out(h, out, 4, 3)) == SLAM_E_NOTPD)
         slam_set_error("FEJ update: S is not positive definite, pivot %d is %g (state left unchanged)", (int)out[3], out[2]);
-        return SLAM_E_NOTPD;
-    }
-    return SLAM_OK;
+    return rc;
 }
 
 extern "C" int slam_ekf_fej_augment(slam_ekf_fej_t f, const double* zn, int cnt, const double R[4]) {

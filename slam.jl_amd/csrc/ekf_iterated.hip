@@ -13,7 +13,8 @@
 // The observations travel in one small block copied into the handle's update workspace (Smat, free in the reference form); the
 // solve kernel appends the Jacobian blocks to it, so H never visits the host.  When an S is not positive definite the solve kernel
 // sets the handle's status word: the panel kernel then writes a ZERO panel and leaves x alone, and the down-date returns at once on
-// the same word.  The block's layout and the panel kernel live in obs_panel.h, which ekf_fej.hip shares.
+// the same word.  What is not the loop itself is shared: the block's layout, the gather, P[a, a] H', the entry of S and the panel
+// kernel with ekf_fej.hip (obs_panel.h); the factorisation and the solve with that file and ekf_linear.hip (small_front.h).
 #include <cmath>
 #include <vector>
 
@@ -21,9 +22,6 @@
 #include "../../include/ext/slamhip_iterated.h"
 #include "device_math.h"
 #include "obs_panel.h"
-
-int launch_downdate(slam_ekf* h, int kp_total, const void* X, const void* Y, int pitch, const int32_t* dcount, int joseph, int k16,
-                    const void* img);      // ekf_syrk.hip
 
 namespace {
 
@@ -40,29 +38,19 @@ __device__ __forceinline__ void eval_model(const double* xs, const double* zs, i
     r[1] = mpi_to_pi_d(zs[2 * o + 1] - om.zp[1]);
 }
 
-// One workgroup of 256.  Thread (i, j) forms S[i][j] and owns that entry in the trailing updates of the factorisation; lane r of the
-// first 16 scales row r of a pivot's column and owns column r of inv(L).  Rows / columns >= k are the identity, so the chain of
-// pivots stops at k.  Every decision (a failing pivot, the stop) is taken from values all threads read from LDS, so it is uniform.
-// status may be null (the dry run).
+// One workgroup of 256, the Gauss-Newton loop around the pieces of obs_panel.h and small_front.h.  Every decision (a failing pivot,
+// the stop) is taken from values all threads read from LDS, so it is uniform.  status may be null (the dry run).
 template <typename T>
 __global__ __launch_bounds__(256) void iterated_solve_kernel(const T* __restrict__ x, const T* __restrict__ P, int ld, double* __restrict__ blob,
                                                               int m, int max_iter, double tol, double* __restrict__ Cout,
                                                               double* __restrict__ gout, double* __restrict__ out, int32_t* __restrict__ status) {
-    constexpr int L = kTileLog2<T>;
     __shared__ double Pa[NA][NA + 1], PaHt[NA][LP], M[LK][LP], S0[LK][LP], Li[LK][LP];
     __shared__ double x0a[NA], xi[NA], xn[NA], du[NA], v[LK], y[LK], g[LK], pr[LK], rr[2][LK], hb[2][MO][HB], zs[LK], Rs[4];
     __shared__ int cols[NA];
     const int tid = threadIdx.x, k = 2 * m, na = 3 + 2 * m;
-    const int32_t* __restrict__ idf = reinterpret_cast<const int32_t*>(blob + B_IDF);
-    if (tid < NA) cols[tid] = tid < 3 ? tid : (tid < na ? 3 + 2 * (idf[(tid - 3) >> 1] - 1) + ((tid - 3) & 1) : 0);
-    if (tid < LK) zs[tid] = tid < k ? blob[B_Z + tid] : 0.0;
-    if (tid < 4) Rs[tid] = blob[B_R + tid];
-    __syncthreads();
-    for (int t = tid; t < na * na; t += 256) {
-        const int r = t / na, c = t - r * na;
-        Pa[r][c] = (double)sym_at(P, ld, L, cols[r], cols[c]);
-    }
-    if (tid < na) x0a[tid] = xi[tid] = (double)x[cols[tid]];
+    obs_tables(blob, m, cols, zs, Rs);
+    obs_gather(x, P, ld, cols, na, Pa, x0a);
+    if (tid < na) xi[tid] = x0a[tid];
     __syncthreads();
     if (tid < m) eval_model(xi, zs, tid, hb[0][tid], &rr[0][2 * tid]);
     __syncthreads();
@@ -74,65 +62,14 @@ __global__ __launch_bounds__(256) void iterated_solve_kernel(const T* __restrict
         if (tid < na) du[tid] = x0a[tid] - xi[tid];
         __syncthreads();
         if (tid < k) v[tid] = rr[b][tid] - h_row_dot(hb[b][tid >> 1], tid >> 1, tid & 1, du);      // v = r - H (x0 - x_i)
-        for (int t = tid; t < na * LK; t += 256) {                              // P[a, a] H'
-            const int r = t >> 4, c = t & 15;
-            PaHt[r][c] = c < k ? h_row_dot(hb[b][c >> 1], c >> 1, c & 1, Pa[r]) : 0.0;
-        }
+        obs_paht(hb[b], Pa, PaHt, k, na);
         __syncthreads();
-        {
-            double s = i == j ? 1.0 : 0.0;
-            if (i < k && j < k) {
-                const int o = i >> 1, q = i & 1;
-                const double* hv = hb[b][o] + 3 * q;
-                const double* hf = hb[b][o] + 6 + 2 * q;
-                s = __builtin_fma(hf[1], PaHt[4 + 2 * o][j], __builtin_fma(hf[0], PaHt[3 + 2 * o][j],
-                    __builtin_fma(hv[2], PaHt[2][j], __builtin_fma(hv[1], PaHt[1][j], hv[0] * PaHt[0][j]))));
-                if ((i >> 1) == (j >> 1)) s += Rs[(j & 1) * 2 + (i & 1)];
-            }
-            M[i][j] = s;
-        }
-        __syncthreads();
-        const double sym = (M[i][j] + M[j][i]) * 0.5;                         // S = (S + S') / 2
-        __syncthreads();
-        M[i][j] = sym;
-        S0[i][j] = sym;
-        __syncthreads();
-        // right-looking Cholesky S = L L'; every thread reads the same pivot
-        // (the same pivots and the same arithmetic per entry as linear_factor_kernel; the trailing update of a pivot is one
-        //  multiply-add per THREAD instead of a loop per lane -- the chain of k pivots is what an iteration costs -- and log det S
-        //  is taken from the factor's diagonal once, after the last iteration)
-        lmin = INFINITY;
-        for (int c = 0; c < k; ++c) {
-            piv = M[c][c];
-            if (!(piv > 0.0) || !(piv < INFINITY)) { fail = c; break; }
-            const double d = sqrt(piv);
-            lmin = d < lmin ? d : lmin;
-            __syncthreads();
-            if (tid >= c && tid < LK) M[tid][c] = M[tid][c] / d;
-            __syncthreads();
-            if (i > c && j > c && j <= i) M[i][j] -= M[i][c] * M[j][c];
-            __syncthreads();
-        }
-        if (fail >= 0) break;
-        if (tid < k) {       // inv(L): lane c solves L X[:, c] = e_c
-            for (int r = 0; r < k; ++r) {
-                double s = r == tid ? 1.0 : 0.0;
-                for (int q = tid; q < r; ++q) s -= M[r][q] * Li[q][tid];
-                Li[r][tid] = r < tid ? 0.0 : s / M[r][r];
-            }
-        }
-        __syncthreads();
-        if (tid < k) {       // y = C' v = inv(L) v
-            double s = 0.0;
-            for (int q = 0; q <= tid; ++q) s += Li[tid][q] * v[q];
-            y[tid] = s;
-        }
-        __syncthreads();
-        if (tid < LK) {      // g = C y = inv(L)' y
-            double s = 0.0;
-            for (int q = tid; q < k; ++q) s += Li[q][tid] * y[q];
-            g[tid] = s;
-        }
+        M[i][j] = obs_s_entry(hb[b], PaHt, Rs, k, i, j);
+        S0[i][j] = small_symmetrise(M);                                       // (read after the next barriers)
+        // log det S is taken from the factor's diagonal once, after the last iteration
+        if ((fail = small_cholesky(M, k, piv, lmin, nullptr)) >= 0) break;
+        const double gl = small_solve(M, Li, v, y, k);
+        if (tid < LK) g[tid] = gl;
         __syncthreads();
         if (tid < na) {      // x_{i+1} = x0 + P[a, a] H' g
             double s = 0.0;
@@ -179,7 +116,7 @@ __global__ __launch_bounds__(256) void iterated_solve_kernel(const T* __restrict
         }
         return;
     }
-    Cout[tid] = (i < k && j < k && i <= j) ? Li[j][i] : 0.0;            // C[i][j] = inv(L)[j][i], zero outside the leading k x k
+    small_store_c(Li, k, Cout);
     if (tid < LK) gout[tid] = tid < k ? g[tid] : 0.0;
     if (tid < m * HB) blob[B_H + tid] = hb[b][tid / HB][tid % HB];       // the Jacobian of the LAST iteration, for the panel
     if (tid == 0) {
@@ -200,41 +137,20 @@ int check_arguments(slam_ekf* h, const double* zf, const int32_t* idf, int m, co
     ARG_CHECK(max_iter >= 1 && max_iter <= SLAM_ITERATED_MAXITER, "max_iter outside 1 .. 64");
     ARG_CHECK(std::isfinite(tol) && tol >= 0.0, "tol is negative or not finite");
     ARG_CHECK(slam_all_finite(zf, 2 * m), "zf is not finite");
-    ARG_CHECK(slam_all_finite(R, 4), "R is not finite");
-    ARG_CHECK(R[1] == R[2], "R is not symmetric");
-    ARG_CHECK(R[0] > 0.0 && R[0] * R[3] - R[1] * R[2] > 0.0, "R is not positive definite");
-    blob.assign(B_IN, 0.0);
-    int32_t* words = reinterpret_cast<int32_t*>(blob.data() + B_IDF);
-    for (int o = 0; o < MO; ++o) words[o] = 1;
-    for (int o = 0; o < m; ++o) {
-        ARG_CHECK(idf[o] >= 1 && idf[o] <= h->N, "idf entry out of range (Julia: BoundsError)");
-        words[o] = idf[o];
-        blob[B_Z + 2 * o] = zf[2 * o];
-        blob[B_Z + 2 * o + 1] = zf[2 * o + 1];
-    }
-    for (int q = 0; q < 4; ++q) blob[B_R + q] = R[q];
-    return SLAM_OK;
+    int rc;
+    if ((rc = check_R(R))) return rc;
+    return obs_block_fill(h, zf, idf, m, R, blob);
 }
 
 template <typename T>
 int enqueue(slam_ekf* h, int m, int max_iter, double tol, bool commit) {
-    const int n = 3 + 2 * h->N;
-    double* blob = h->Smat;
     {
         KTimer t(h, SLAM_K_FACTOR);
-        hipLaunchKernelGGL(iterated_solve_kernel<T>, dim3(1), dim3(256), 0, h->stream, (const T*)h->x, (const T*)h->P, h->ld, blob, m, max_iter,
+        hipLaunchKernelGGL(iterated_solve_kernel<T>, dim3(1), dim3(256), 0, h->stream, (const T*)h->x, (const T*)h->P, h->ld, h->Smat, m, max_iter,
                            tol, h->Cmat, h->gvec, h->d_small, commit ? h->d_status : (int32_t*)nullptr);
     }
     HIP_TRY(hipGetLastError());
-    if (!commit) return SLAM_OK;
-    {
-        KTimer t(h, SLAM_K_W1);
-        hipLaunchKernelGGL(iterated_panel_kernel<T>, dim3((h->npad + PANEL_THREADS - 1) / PANEL_THREADS), dim3(PANEL_THREADS), 0, h->stream,
-                           (T*)h->x, (const T*)h->P, h->ld, n, h->npad, (const double*)blob, m, (const double*)h->Cmat,
-                           (const double*)h->gvec, (T*)h->W1, 2 * h->kcap, (const int32_t*)h->d_status);
-    }
-    HIP_TRY(hipGetLastError());
-    return launch_downdate(h, LK, h->W1, h->W1, 2 * h->kcap, (const int32_t*)nullptr, 0, LK, nullptr);
+    return commit ? enqueue_obs_panel<T>(h, m) : SLAM_OK;
 }
 
 int iterated_call(slam_ekf* h, const double* zf, const int32_t* idf, int m, const double* R, int max_iter, double tol, double* out,
@@ -249,15 +165,10 @@ int iterated_call(slam_ekf* h, const double* zf, const int32_t* idf, int m, cons
     rc = h->dtype == SLAM_F32 ? enqueue<float>(h, m, max_iter, tol, commit) : enqueue<double>(h, m, max_iter, tol, commit);
     if (rc) return rc;
     if (commit) h->grid_force = 1;                                        // the means moved: the grid is rebuilt at the next query
-    HIP_TRY(hipMemcpyAsync(h->h_small, h->d_small, sizeof(double) * OUTN, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    for (int q = 0; q < OUTN; ++q) out[q] = h->h_small[q];
-    if (out[6] >= 0.0) {
+    if ((rc = slam_small_out(h, out, OUTN, 6)) == SLAM_E_NOTPD)
         slam_set_error("iterated update: S is not positive definite at iteration %d, pivot %d is %g (state left unchanged)", (int)out[7],
                        (int)out[6], out[5]);
-        return SLAM_E_NOTPD;
-    }
-    return SLAM_OK;
+    return rc;
 }
 
 }  // namespace

@@ -4,8 +4,9 @@
 //
 // UPDATE.  The reference's Cholesky-form update (src/ekf.jl:67-75) for k <= 16 sparse rows of H in CSR, the shape of the merge
 // (ekf_merge.hip) with the caller's rows in place of +I2 / -I2:
-//     linear_factor_kernel  (one workgroup)       S = H P H' + R entry by entry from the symmetric view of P, symmetrised, chol,
-//                                                  C = inv(chol(S)), g = C C' v, the four numbers of `out`; all in double
+//     linear_factor_kernel  (one workgroup)       S = H P H' + R entry by entry from the symmetric view of P, then the pieces of
+//                                                  small_front.h: symmetrised, chol, C = inv(chol(S)), g = C C' v; the four
+//                                                  numbers of `out`; all in double
 //     linear_panel_kernel   (a thread per row r)   PHt[r, :] from the row's <= 8 non-zeros, W1[r, :] = PHt[r, :] C as the handle's
 //                                                  dtype, zero-padded to 16 columns, x[r] += PHt[r, :] g
 //     launch_downdate                              P -= W1 W1' on the plain 16-column panel (ekf_syrk.hip), which also keeps Pside
@@ -15,7 +16,7 @@
 //
 // PREDICT.  linear_strip_kernel, one launch over the vehicle's three columns of the tile-major matrix as predict_kernel
 // (ekf_strip.hip) walks them: thread f >= 3 owns row f of the column strip and its mirror; the workgroup that arrives last, i.e.
-// after every workgroup has read the heading, rewrites P_vv and the pose.  Gv and Qv come from the caller (predict_linear) or
+// after every workgroup has read the heading, rewrites P_vv and the pose (strip_tail.h).  Gv and Qv come from the caller (predict_linear) or
 // are formed from x[2] and the increment on the device (predict_odometry).
 #include <cmath>
 #include <vector>
@@ -23,14 +24,12 @@
 #include "common.h"
 #include "../../include/ext/slamhip_linear.h"
 #include "device_math.h"
-
-int launch_downdate(slam_ekf* h, int kp_total, const void* X, const void* Y, int pitch, const int32_t* dcount, int joseph, int k16,
-                    const void* img);      // ekf_syrk.hip
+#include "small_front.h"
+#include "strip_tail.h"
 
 namespace {
 
-constexpr int LK = SLAM_LINEAR_MAXROWS;                    // 16: the panel's columns, one chunk of the down-date
-constexpr int LP = LK + 1;
+static_assert(SLAM_LINEAR_MAXROWS == LK, "the rows fill the 16 x 16 front half");
 constexpr int LNZ = SLAM_LINEAR_MAXROWS * SLAM_LINEAR_MAXNNZ;
 // LinBlob, in doubles: R as 16 x 16 (symmetric, zero outside k x k), z, val, then int32 words: ptr[17] and, from word 20, idx[128]
 constexpr int B_R = 0, B_Z = LK * LK, B_VAL = B_Z + LK, B_INT = B_VAL + LNZ, B_IDX_WORD = 20;
@@ -63,10 +62,10 @@ __device__ __forceinline__ double linear_pht(const T* __restrict__ P, int ld, in
     return s;
 }
 
-// One workgroup of 256: thread (i, j) forms S[i][j]; then lane i of the first 16 owns row i of the factorisation, as in
-// merge_factor_kernel.  Rows / columns >= k are the identity, so the chain of pivots stops at k.  out4 = {v' inv(S) v,
-// log det S, min l_jj, -1} or, when pivot j fails, {0, 0, d_j, j} and nothing else is written.  status (may be null: the gate
-// alone) gets 0 / 1.
+// One workgroup of 256: thread (i, j) forms S[i][j], lane i of the first 16 v[i]; small_front.h does the rest.  out4 = {v' inv(S) v,
+// log det S, min l_jj, -1} or, when pivot j fails, {0, 0, d_j, j} and nothing else is written.  log det S is summed, ascending, over
+// the l_jj as the chain took their square roots: they wait in y, which is free until the solve, and a lane of the second wave --
+// idle while the first inverts L -- takes the logarithms.  status (may be null: the gate alone) gets 0 / 1.
 template <typename T>
 __global__ __launch_bounds__(256) void linear_factor_kernel(const T* __restrict__ x, const T* __restrict__ P, int ld,
                                                              const double* __restrict__ blob, int k, int mode, unsigned wrap,
@@ -101,29 +100,9 @@ __global__ __launch_bounds__(256) void linear_factor_kernel(const T* __restrict_
         }
         v[tid] = d;
     }
-    __syncthreads();
-    const double sym = (M[i][j] + M[j][i]) * 0.5;                         // S = (S + S') / 2
-    __syncthreads();
-    M[i][j] = sym;
-    __syncthreads();
-    // right-looking Cholesky S = L L', lane r owns row r; every thread reads the same pivot, so the decisions are uniform
-    int fail = -1;
-    double piv = 0.0, lmin = INFINITY, lsum = 0.0;
-    for (int c = 0; c < k; ++c) {
-        piv = M[c][c];
-        if (!(piv > 0.0) || !(piv < INFINITY)) { fail = c; break; }
-        const double d = sqrt(piv);
-        lmin = d < lmin ? d : lmin;
-        lsum += log(d);
-        __syncthreads();
-        if (tid >= c && tid < LK) M[tid][c] = M[tid][c] / d;
-        __syncthreads();
-        if (tid > c && tid < LK) {
-            const double lrc = M[tid][c];
-            for (int q = c + 1; q <= tid; ++q) M[tid][q] -= lrc * M[q][c];
-        }
-        __syncthreads();
-    }
+    small_symmetrise(M);
+    double piv = 0.0, lmin;
+    const int fail = small_cholesky(M, k, piv, lmin, y);
     if (fail >= 0) {
         if (tid == 0) {
             out4[0] = 0.0; out4[1] = 0.0; out4[2] = piv; out4[3] = (double)fail;
@@ -131,30 +110,18 @@ __global__ __launch_bounds__(256) void linear_factor_kernel(const T* __restrict_
         }
         return;
     }
-    if (tid < k) {       // inv(L): lane c solves L X[:, c] = e_c
-        for (int r = 0; r < k; ++r) {
-            double s = r == tid ? 1.0 : 0.0;
-            for (int m = tid; m < r; ++m) s -= M[r][m] * Li[m][tid];
-            Li[r][tid] = r < tid ? 0.0 : s / M[r][r];
-        }
+    if (tid == 64) {
+        double lsum = 0.0;
+        for (int c = 0; c < k; ++c) lsum += log(y[c]);
+        out4[1] = 2.0 * lsum;
     }
-    __syncthreads();
-    if (tid < k) {       // y = C' v = inv(L) v
-        double s = 0.0;
-        for (int m = 0; m <= tid; ++m) s += Li[tid][m] * v[m];
-        y[tid] = s;
-    }
-    __syncthreads();
-    if (tid < LK) {      // g = C y = inv(L)' y
-        double s = 0.0;
-        for (int m = tid; m < k; ++m) s += Li[m][tid] * y[m];
-        gout[tid] = s;                                                    // (no term for tid >= k)
-    }
-    Cout[tid] = (i < k && j < k && i <= j) ? Li[j][i] : 0.0;            // C[i][j] = inv(L)[j][i], zero outside the leading k x k
+    const double gl = small_solve(M, Li, v, y, k);
+    if (tid < LK) gout[tid] = gl;
+    small_store_c(Li, k, Cout);
     if (tid == 0) {
         double nis = 0.0;
         for (int m = 0; m < k; ++m) nis += y[m] * y[m];
-        out4[0] = nis; out4[1] = 2.0 * lsum; out4[2] = lmin; out4[3] = -1.0;
+        out4[0] = nis; out4[2] = lmin; out4[3] = -1.0;
         if (status) status[0] = 0;
     }
 }
@@ -243,14 +210,9 @@ __global__ __launch_bounds__(256) void linear_strip_kernel(T* __restrict__ x, T*
         for (int c = 0; c < 3; ++c)       // column strip P[f, 0:3] = P[f, 0:3] Gv'; its mirror exists inside the first tile only
             p_store_sym(P, ld, tlog, f, c, (T)(G[c][0] * p0 + G[c][1] * p1 + G[c][2] * p2));
     }
-    __shared__ int last;
-    __syncthreads();                         // every thread of the workgroup has its heading
-    if (threadIdx.x == 0)
-        last = __hip_atomic_fetch_add(arrive, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (int)gridDim.x - 1;
-    __syncthreads();
-    if (!last || threadIdx.x != 0) return;
-    __hip_atomic_store(arrive, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);          // re-armed
-    double Qs[3][3], Qv[3][3], Pvv[3][3], GP[3][3];
+    if (!strip_arrive_last(arrive) || threadIdx.x != 0) return;
+    strip_rearm(arrive);
+    double Qs[3][3], Qv[3][3];
 #pragma unroll
     for (int r = 0; r < 3; ++r)
 #pragma unroll
@@ -266,17 +228,7 @@ __global__ __launch_bounds__(256) void linear_strip_kernel(T* __restrict__ x, T*
         for (int r = 0; r < 3; ++r)
             for (int c = 0; c <= r; ++c) Qv[r][c] = Qs[r][c];
     }
-    for (int r = 0; r < 3; ++r)
-        for (int c = 0; c < 3; ++c) Pvv[r][c] = (double)P[p_off(ld, tlog, r, c)];
-    for (int r = 0; r < 3; ++r)
-        for (int c = 0; c < 3; ++c) GP[r][c] = G[r][0] * Pvv[0][c] + G[r][1] * Pvv[1][c] + G[r][2] * Pvv[2][c];
-    // the lower triangle, each entry formed once and mirrored: (r, c) and (c, r) formed separately round differently
-    for (int r = 0; r < 3; ++r)
-        for (int c = 0; c <= r; ++c) {
-            const T val = (T)((GP[r][0] * G[c][0] + GP[r][1] * G[c][1] + GP[r][2] * G[c][2]) + Qv[r][c]);
-            P[p_off(ld, tlog, r, c)] = val;
-            P[p_off(ld, tlog, c, r)] = val;
-        }
+    strip_rewrite_pvv(P, ld, tlog, G, Qv);
     x[0] = (T)xn[0];
     x[1] = (T)xn[1];
     x[2] = (T)xn[2];
@@ -353,14 +305,9 @@ int linear_call(slam_ekf* h, int k, const int32_t* ptr, const int32_t* idx, cons
     rc = h->dtype == SLAM_F32 ? enqueue_front<float>(h, k, mode, wrap_mask, commit) : enqueue_front<double>(h, k, mode, wrap_mask, commit);
     if (rc) return rc;
     if (commit) h->grid_force = 1;                                        // the means moved: the grid is rebuilt at the next query
-    HIP_TRY(hipMemcpyAsync(h->h_small, h->d_small, sizeof(double) * 4, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    for (int i = 0; i < 4; ++i) out[i] = h->h_small[i];
-    if (out[3] >= 0.0) {
+    if ((rc = slam_small_out(h, out, 4, 3)) == SLAM_E_NOTPD)
         slam_set_error("linear measurement: S is not positive definite, pivot %d is %g (state left unchanged)", (int)out[3], out[2]);
-        return SLAM_E_NOTPD;
-    }
-    return SLAM_OK;
+    return rc;
 }
 
 int strip_call(slam_ekf* h, const StripArgs& A) {

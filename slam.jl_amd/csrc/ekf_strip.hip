@@ -12,6 +12,7 @@
 // (:108-109); here the capacity was allocated once at create.
 #include "common.h"
 #include "device_math.h"
+#include "strip_tail.h"
 
 namespace {
 
@@ -272,8 +273,7 @@ namespace {
 
 // E1 as ONE launch (the reference's sim! calls predict nine times per observation step: launches are what it costs).
 // Every workgroup needs the PRE-update heading for the strip; the pose and P_vv are rewritten by whichever
-// workgroup arrives LAST at the counter, i.e. after every workgroup has read x[2].  Nothing is published between
-// workgroups (the strip and the pose block are disjoint), so the arrival is a relaxed atomic without fences.
+// workgroup arrives LAST at the counter, i.e. after every workgroup has read x[2] (strip_tail.h).
 template <typename T>
 __global__ __launch_bounds__(256) void predict_kernel(T* __restrict__ x, T* __restrict__ P, int ld, int n, double v, double g,
                                                        double w, double Q0, double Q1, double Q2, double Q3, double dt,
@@ -293,33 +293,13 @@ __global__ __launch_bounds__(256) void predict_kernel(T* __restrict__ x, T* __re
         p_store_sym(P, ld, tlog, f, 1, n1);
         p_store_sym(P, ld, tlog, f, 2, n2);
     }
-    __shared__ int last;
-    __syncthreads();                         // every thread of the workgroup has its heading
-    if (threadIdx.x == 0)
-        last = __hip_atomic_fetch_add(arrive, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (int)gridDim.x - 1;
-    __syncthreads();
-    if (!last || threadIdx.x != 0) return;
-    __hip_atomic_store(arrive, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);          // re-armed
+    if (!strip_arrive_last(arrive) || threadIdx.x != 0) return;
+    strip_rearm(arrive);
     const double Gv[3][3] = {{1.0, 0.0, -vts}, {0.0, 1.0, vtc}, {0.0, 0.0, 1.0}};
     const double Gu[3][2] = {{dt * cs, -vts}, {dt * sn, vtc}, {dt * sin(g) / w, v * dt * cos(g) / w}};
-    const double Q[2][2] = {{Q0, Q2}, {Q1, Q3}};   // column-major input
-    double Pvv[3][3], GP[3][3], GQ[3][2], out[3][3];
-    for (int r = 0; r < 3; ++r)
-        for (int cc = 0; cc < 3; ++cc) Pvv[r][cc] = (double)P[p_off(ld, tlog, r, cc)];
-    for (int r = 0; r < 3; ++r)
-        for (int cc = 0; cc < 3; ++cc)
-            GP[r][cc] = Gv[r][0] * Pvv[0][cc] + Gv[r][1] * Pvv[1][cc] + Gv[r][2] * Pvv[2][cc];
-    for (int r = 0; r < 3; ++r)
-        for (int cc = 0; cc < 2; ++cc) GQ[r][cc] = Gu[r][0] * Q[0][cc] + Gu[r][1] * Q[1][cc];
-    // the lower triangle, each entry formed once and mirrored: (r, cc) and (cc, r) formed separately round differently
-    for (int r = 0; r < 3; ++r)
-        for (int cc = 0; cc <= r; ++cc) {
-            out[r][cc] = (GP[r][0] * Gv[cc][0] + GP[r][1] * Gv[cc][1] + GP[r][2] * Gv[cc][2]) +
-                         (GQ[r][0] * Gu[cc][0] + GQ[r][1] * Gu[cc][1]);
-            out[cc][r] = out[r][cc];
-        }
-    for (int r = 0; r < 3; ++r)
-        for (int cc = 0; cc < 3; ++cc) P[p_off(ld, tlog, r, cc)] = (T)out[r][cc];
+    double GQG[3][3];
+    strip_gu_q_gut(Gu, Q0, Q1, Q2, Q3, GQG);
+    strip_rewrite_pvv(P, ld, tlog, Gv, GQG);
     const double x0 = (double)x[0], x1 = (double)x[1];
     x[0] = (T)(x0 + vtc);
     x[1] = (T)(x1 + vts);

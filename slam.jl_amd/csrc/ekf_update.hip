@@ -20,9 +20,6 @@
 #include "common.h"
 #include "device_math.h"
 
-int launch_downdate(slam_ekf* h, int kp_total, const void* X, const void* Y, int pitch, const int32_t* dcount, int joseph, int k16,
-                    const void* img);   // ekf_syrk.hip
-
 namespace {
 
 // observe(): the host launches with an upper bound of the matched count; the kernels read the real one.

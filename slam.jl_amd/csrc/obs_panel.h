@@ -1,15 +1,19 @@
-// obs_panel.h -- what the updates that take up to 8 range-bearing observations share behind their front halves (ekf_iterated.hip,
-// ekf_fej.hip): the block the observations travel in, the five non-zeros of a row of H, and the panel kernel that forms the PHt rows,
-// W1 and the mean from the Jacobian blocks a front half left in that block -- wherever it evaluated them.
+// obs_panel.h -- what the updates that take up to 8 range-bearing observations share (ekf_iterated.hip, ekf_fej.hip): the block the
+// observations travel in and the host code that fills it; the pieces of a front half that do not depend on where the Jacobian was
+// evaluated (the gather of P[a, a] and x[a], P[a, a] H', an entry of S; small_front.h factors and solves); the panel kernel that
+// forms the PHt rows, W1 and the mean from the Jacobian blocks a front half left in that block; and the enqueue of that kernel and
+// the down-date.
 #pragma once
+
+#include <vector>
 
 #include "common.h"
 #include "../../include/ext/slamhip_iterated.h"
 #include "device_math.h"
+#include "small_front.h"
 
 constexpr int MO = SLAM_ITERATED_MAXOBS;                   // 8 observations
-constexpr int LK = 2 * MO;                                 // 16: the panel's columns, one chunk of the down-date
-constexpr int LP = LK + 1;
+static_assert(2 * MO == LK, "the observations' rows fill the 16 x 16 front half");
 constexpr int NA = 3 + 2 * MO;                             // 19: the states H touches
 constexpr int HB = 10;                                     // one observation's Jacobian blocks: Hv (2 x 3, row-major), Hf (2 x 2)
 // the block in Smat, in doubles: z[16], R[4] (column-major), idf as int32[8], then -- written by the solve kernel -- Hv | Hf of
@@ -21,6 +25,49 @@ __device__ __forceinline__ double h_row_dot(const double* hbo, int o, int q, con
     const double* hv = hbo + 3 * q;
     const double* hf = hbo + 6 + 2 * q;
     return __builtin_fma(hf[1], u[4 + 2 * o], __builtin_fma(hf[0], u[3 + 2 * o], __builtin_fma(hv[2], u[2], __builtin_fma(hv[1], u[1], hv[0] * u[0]))));
+}
+
+// ---- the front half, one workgroup of 256 on the calling kernel's LDS arrays: k = 2m rows, na = 3 + 2m reduced states -----------------
+// the reduced states' indices, z and R from the block; ends on a barrier
+__device__ __forceinline__ void obs_tables(const double* __restrict__ blob, int m, int* cols, double* zs, double* Rs) {
+    const int tid = threadIdx.x, k = 2 * m, na = 3 + 2 * m;
+    const int32_t* __restrict__ idf = reinterpret_cast<const int32_t*>(blob + B_IDF);
+    if (tid < NA) cols[tid] = tid < 3 ? tid : (tid < na ? 3 + 2 * (idf[(tid - 3) >> 1] - 1) + ((tid - 3) & 1) : 0);
+    if (tid < LK) zs[tid] = tid < k ? blob[B_Z + tid] : 0.0;
+    if (tid < 4) Rs[tid] = blob[B_R + tid];
+    __syncthreads();
+}
+
+// P[a, a] and x[a] through cols[]; visible after the caller's next barrier
+template <typename T>
+__device__ __forceinline__ void obs_gather(const T* __restrict__ x, const T* __restrict__ P, int ld, const int* cols, int na,
+                                           double (*Pa)[NA + 1], double* xa) {
+    const int tid = threadIdx.x;
+    for (int t = tid; t < na * na; t += 256) {
+        const int r = t / na, c = t - r * na;
+        Pa[r][c] = (double)sym_at(P, ld, kTileLog2<T>, cols[r], cols[c]);
+    }
+    if (tid < na) xa[tid] = (double)x[cols[tid]];
+}
+
+// P[a, a] H' from the Jacobian blocks hb; visible after the caller's next barrier
+__device__ __forceinline__ void obs_paht(const double (*hb)[HB], const double (*Pa)[NA + 1], double (*PaHt)[LP], int k, int na) {
+    for (int t = threadIdx.x; t < na * LK; t += 256) {
+        const int r = t >> 4, c = t & 15;
+        PaHt[r][c] = c < k ? h_row_dot(hb[c >> 1], c >> 1, c & 1, Pa[r]) : 0.0;
+    }
+}
+
+// S[i][j] = H[i, :] (P[a, a] H')[:, j] + (I (x) R)[i][j]; the identity outside the leading k x k
+__device__ __forceinline__ double obs_s_entry(const double (*hb)[HB], const double (*PaHt)[LP], const double* Rs, int k, int i, int j) {
+    if (i >= k || j >= k) return i == j ? 1.0 : 0.0;
+    const int o = i >> 1, q = i & 1;
+    const double* hv = hb[o] + 3 * q;
+    const double* hf = hb[o] + 6 + 2 * q;
+    double s = __builtin_fma(hf[1], PaHt[4 + 2 * o][j], __builtin_fma(hf[0], PaHt[3 + 2 * o][j],
+               __builtin_fma(hv[2], PaHt[2][j], __builtin_fma(hv[1], PaHt[1][j], hv[0] * PaHt[0][j]))));
+    if ((i >> 1) == (j >> 1)) s += Rs[(j & 1) * 2 + (i & 1)];
+    return s;
 }
 
 // One thread per row r of the PANEL (npad rows: the rows >= n are written as zero, the down-date has no row guards), one wave a
@@ -111,4 +158,41 @@ __global__ __launch_bounds__(PANEL_THREADS) void iterated_panel_kernel(T* __rest
 #pragma unroll
     for (int c = 0; c < LK; ++c) w[c] = (T)acc[c];
     x[r] = (T)(xr + dxr);
+}
+
+// ---- host side ------------------------------------------------------------------------------------------------------------------------
+// the noise rule of the range-bearing updates
+static inline int check_R(const double* R) {
+    ARG_CHECK(slam_all_finite(R, 4), "R is not finite");
+    ARG_CHECK(R[1] == R[2], "R is not symmetric");
+    ARG_CHECK(R[0] > 0.0 && R[0] * R[3] - R[1] * R[2] > 0.0, "R is not positive definite");
+    return SLAM_OK;
+}
+
+// the block for m checked-finite observations and a checked R; the rule it adds: every idf names a landmark of the state
+static inline int obs_block_fill(const slam_ekf* h, const double* zf, const int32_t* idf, int m, const double* R, std::vector<double>& blob) {
+    blob.assign(B_IN, 0.0);
+    int32_t* words = reinterpret_cast<int32_t*>(blob.data() + B_IDF);
+    for (int o = 0; o < MO; ++o) words[o] = 1;
+    for (int o = 0; o < m; ++o) {
+        ARG_CHECK(idf[o] >= 1 && idf[o] <= h->N, "idf entry out of range (Julia: BoundsError)");
+        words[o] = idf[o];
+        blob[B_Z + 2 * o] = zf[2 * o];
+        blob[B_Z + 2 * o + 1] = zf[2 * o + 1];
+    }
+    for (int q = 0; q < 4; ++q) blob[B_R + q] = R[q];
+    return SLAM_OK;
+}
+
+// behind a front half that left C, g, the status word and the Jacobian blocks: the panel, then P -= W1 W1' on its 16 columns
+template <typename T>
+static int enqueue_obs_panel(slam_ekf* h, int m) {
+    {
+        KTimer t(h, SLAM_K_W1);
+        hipLaunchKernelGGL(iterated_panel_kernel<T>, dim3((h->npad + PANEL_THREADS - 1) / PANEL_THREADS), dim3(PANEL_THREADS), 0, h->stream,
+                           (T*)h->x, (const T*)h->P, h->ld, 3 + 2 * h->N, h->npad, (const double*)h->Smat, m, (const double*)h->Cmat,
+                           (const double*)h->gvec, (T*)h->W1, 2 * h->kcap, (const int32_t*)h->d_status);
+    }
+    HIP_TRY(hipGetLastError());
+    return launch_downdate(h, LK, h->W1, h->W1, 2 * h->kcap, (const int32_t*)nullptr, 0, LK, nullptr);
 }
