@@ -24,7 +24,8 @@ export SlamState, EKFSlamState, set_state!, predict, update, add_features, assoc
        step_proposal_unknown!, associate_proposal, proposal_max_obs,
        LocalArea, open_area!, close!, abort!, landmarks_within, accumulators, area_info, global_ids, local_state,
        update_iterated!, iterated_nis, observe_iterated!, iterated_limits,
-       FirstEstimates, fej, predict!, update!, reset!, remap!, linearisation, set_linearisation!, fej_limits
+       FirstEstimates, fej, predict!, update!, reset!, remap!, linearisation, set_linearisation!, fej_limits,
+       update_joint!, wide_limits
 
 const libslamhip = get(ENV, "SLAMHIP_LIB", joinpath(@__DIR__, "libslamhip.so"))
 # the companion library of include/slamhip_frame.h (the rigid frame change); it links against libslamhip.so and lies beside it
@@ -70,6 +71,9 @@ const libslamhip_iterated = get(ENV, "SLAMHIP_ITERATED_LIB", joinpath(@__DIR__, 
 # the extension library of include/ext/slamhip_fej.h (first-estimates Jacobian predict, update and augment for the EKF), same
 # arrangement (opened at the first FirstEstimates / fej_limits)
 const libslamhip_fej = get(ENV, "SLAMHIP_FEJ_LIB", joinpath(@__DIR__, "libslamhip_fej.so"))
+# the extension library of include/ext/slamhip_wide.h (the joint update of up to 64 observations in one down-date), same arrangement
+# (opened at the first update_joint! / joint_nis / wide_limits; it reads a FirstEstimates object and calls nothing of libslamhip_fej.so)
+const libslamhip_wide = get(ENV, "SLAMHIP_WIDE_LIB", joinpath(@__DIR__, "libslamhip_wide.so"))
 
 const SLAM_OK = Cint(0)
 const SLAM_PF_HALTED = Cint(1)
@@ -838,6 +842,52 @@ function set_linearisation!(f::FirstEstimates, lin::AbstractVector, first::Abstr
     check(ccall((:slam_ekf_fej_set, libslamhip_fej), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}),
                 f.handle, Vector{Float64}(lin), Matrix{Float64}(first)))
     nothing
+end
+
+# ---- the joint update of up to 64 observations (include/ext/slamhip_wide.h; written beside the Python binding, never executed) -----
+"    wide_limits() -> observations per joint update call as libslamhip_wide.so reports them."
+function wide_limits()
+    out = zeros(Int32, 1)
+    check(ccall((:slam_ekf_wide_limits, libslamhip_wide), Cint, (Ptr{Int32},), out))
+    Int(out[1])
+end
+
+# the batches of 64 of update_joint! (commit) and the one call of joint_nis; fh: the FirstEstimates handle, or C_NULL (the stored state)
+function wide_batches(commit::Bool, sh::Ptr{Cvoid}, fh::Ptr{Cvoid}, z::AbstractMatrix, R::AbstractMatrix, idf)
+    m = size(z, 2)
+    ids = Vector{Int32}(vec(collect(idf)))
+    length(ids) == m || throw(ArgumentError("idf and z disagree on the number of observations"))
+    zz, r = pairs64(z), colmajor4(R)
+    outs = zeros(Float64, 4, cld(m, 64))
+    for (b, lo) in enumerate(1:64:m)
+        hi = min(lo + 63, m)
+        out = zeros(Float64, 4)
+        if commit
+            check(ccall((:slam_ekf_wide_update, libslamhip_wide), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Int32}, Cint, Ptr{Cdouble}, Ptr{Cdouble}),
+                        sh, fh, zz[:, lo:hi], ids[lo:hi], hi - lo + 1, r, out))
+        else
+            check(ccall((:slam_ekf_wide_nis, libslamhip_wide), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Int32}, Cint, Ptr{Cdouble}, Ptr{Cdouble}),
+                        sh, fh, zz[:, lo:hi], ids[lo:hi], hi - lo + 1, r, out))
+        end
+        outs[:, b] = out
+    end
+    outs
+end
+
+"""
+    update_joint!(f, z, R, idf) -> 4 x batches matrix of [v' inv(S) v, log det S, smallest pivot, -1]
+
+`update!(f, ...)` of up to 64 observations JOINTLY, in one pass over the covariance: every residual at the mean before the call, every
+Jacobian at lin and the first estimates.  More than 64 go as consecutive batches of 64.  `update_joint!(s, z, R, idf)` on a state
+takes the Jacobians at the stored state: the Cholesky-form `ekf_update!` by the wide front half.
+"""
+update_joint!(f::FirstEstimates, z::AbstractMatrix, R::AbstractMatrix, idf) = wide_batches(true, handle(f.state), f.handle, z, R, idf)
+update_joint!(s::EKFSlamState, z::AbstractMatrix, R::AbstractMatrix, idf) = wide_batches(true, handle(s), C_NULL, z, R, idf)
+
+"    joint_nis(f, z, R, idf) -> what update_joint! would return for at most 64 observations, the state only read."
+function joint_nis(f::FirstEstimates, z::AbstractMatrix, R::AbstractMatrix, idf)
+    size(z, 2) <= 64 || throw(ArgumentError("joint_nis takes at most 64 observations"))
+    wide_batches(false, handle(f.state), f.handle, z, R, idf)
 end
 
 # ---- compressed local-area updates (include/ext/slamhip_local.h) -----------------------------------------------------------------

@@ -434,6 +434,21 @@ fej_lib = Companion("fej", FEJ_SIGNATURES)
 FEJ_LIB_PATH = fej_lib.path
 
 
+# ---- wide: the joint update of up to 64 observations in one down-date, opened at the first such call --------------------------------
+# Wired like fej, and like it entered in neither table; its surface checks are made by tests/test_wide_ref_cpu.py.
+SLAM_WIDE_MAXOBS = 64
+
+#: every symbol include/ext/slamhip_wide.h declares
+WIDE_SIGNATURES = {
+    "slam_ekf_wide_update": (C.c_int, [_h, _h, _dp, _ip, C.c_int, _dp, _dp]),
+    "slam_ekf_wide_nis": (C.c_int, [_h, _h, _dp, _ip, C.c_int, _dp, _dp]),
+    "slam_ekf_wide_limits": (C.c_int, [_ip]),
+}
+
+wide_lib = Companion("wide", WIDE_SIGNATURES)
+WIDE_LIB_PATH = wide_lib.path
+
+
 def proposal_max_obs() -> int:
     """Observations per call of the proposal step with unknown correspondences, as the library reports it."""
     out = (C.c_int * 4)()

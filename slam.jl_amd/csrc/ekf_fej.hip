@@ -23,18 +23,9 @@
 #include "common.h"
 #include "../../include/ext/slamhip_fej.h"
 #include "device_math.h"
+#include "fej_object.h"
 #include "obs_panel.h"
 #include "strip_tail.h"
-
-struct slam_ekf_fej {
-    slam_ekf* h;
-    int N;             // the landmarks the object knows: h->N, unless the map changed outside (remap)
-    int maxN;          // h->maxN at create: the capacity of the arrays below
-    double* lin;       // [3]         the vehicle's linearisation pose
-    double* first;     // [2 maxN]    every landmark's first estimate
-    double* spare;     // [2 maxN]    remap writes here; the two are swapped
-    int32_t* ids;      // [maxN]      reset / remap: the ids
-};
 
 namespace {
 

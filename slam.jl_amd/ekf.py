@@ -878,6 +878,12 @@ class EKFSlamState(SlamState):
         three unobservable directions of the map.  It starts from the current estimates and is closed with the state."""
         return FirstEstimates(self)
 
+    def update_joint_at_estimates(self, zf, R, idf):
+        """``update`` (Cholesky form) of up to 64 observations per call through the wide front half of libslamhip_wide.so with the
+        Jacobians at the stored state (slam_ekf_wide_update without a first-estimates object): the same estimator as ``update``,
+        by other kernels -- the cross-check of :meth:`FirstEstimates.update_joint`.  Returns one row of ``out`` per batch of 64."""
+        return _wide_batches(_lib.wide_lib().slam_ekf_wide_update, self._h, None, zf, R, idf)
+
     def transform(self, tx, ty, theta):
         """Express the whole state in another frame, in place on the device (slam_ekf_transform): every position becomes
         R(theta) p + (tx, ty), the heading mpi_to_pi(phi + theta), cov becomes T cov T' with T = blockdiag(R, 1, R, R, ...).
@@ -1225,6 +1231,23 @@ class CovarianceFactor:
         return self.mean()[:, None] + self.colour(Z)
 
 
+def _wide_batches(fn, h, f, zf, R, idf):
+    """One call of libslamhip_wide.so per 64 observations; f: the first-estimates object's handle, or None (the stored state)."""
+    zp = _obs(zf)
+    ids = np.ascontiguousarray(np.asarray(idf, dtype=np.int32).reshape(-1))
+    if ids.shape[0] != zp.shape[0]:
+        raise ValueError("idf and z disagree on the number of observations")
+    if zp.shape[0] == 0:
+        return None
+    r = _small(R)
+    B = _lib.SLAM_WIDE_MAXOBS
+    outs = np.zeros(((zp.shape[0] + B - 1) // B, 4))
+    for b, s in enumerate(range(0, zp.shape[0], B)):
+        zb, ib = np.ascontiguousarray(zp[s:s + B]), np.ascontiguousarray(ids[s:s + B])
+        check(fn(h, f, _ptr(zb), _ptr(ib, C.c_int32), zb.shape[0], _ptr(r), _ptr(outs[b])))
+    return outs
+
+
 class FirstEstimates:
     """The linearisation points of a first-estimates Jacobian (FEJ) filter over ``state`` (include/ext/slamhip_fej.h), on the device
     beside the state: ``lin``, the pose the vehicle's Jacobians are evaluated at (the predicted pose, never an updated one), and
@@ -1333,6 +1356,25 @@ class FirstEstimates:
             check(self._lib.slam_ekf_fej_update(self._f, _ptr(zb), _ptr(ib, C.c_int32), zb.shape[0], _ptr(r), _ptr(outs[b])))
         return outs
 
+    def _wide(self, fn, zf, R, idf):
+        return _wide_batches(fn, self.state._h, self._f, zf, R, idf)
+
+    def update_joint(self, zf, R, idf):
+        """:meth:`update` of up to 64 observations JOINTLY, in one pass over the covariance (slam_ekf_wide_update): every residual
+        is taken at the mean before the call, every Jacobian at ``lin`` and the first estimates.  This is the filter's own update
+        of the whole batch; ``update`` with more than 8 observations is a chain of 8-observation updates and a different
+        estimator.  More than 64 go as consecutive batches of 64.  Returns one row ``[v' inv(S) v, log det S, smallest pivot, -1]``
+        per batch (None without an observation); raises NotPositiveDefinite with the state unchanged by the failing batch."""
+        return self._wide(_lib.wide_lib().slam_ekf_wide_update, zf, R, idf)
+
+    def joint_nis(self, zf, R, idf):
+        """What :meth:`update_joint` would return, with the state only read (slam_ekf_wide_nis): the joint chi-square gate of a
+        whole batch at the linearisation points before it is committed.  At most 64 observations: a second batch would have to
+        start from the state the first one leaves."""
+        if _obs(zf).shape[0] > _lib.SLAM_WIDE_MAXOBS:
+            raise ValueError("joint_nis takes at most 64 observations")
+        return self._wide(_lib.wide_lib().slam_ekf_wide_nis, zf, R, idf)
+
     def add_features(self, zn, R):
         """``state.add_features`` with the new landmarks' Jacobians taken between ``lin`` and their new means, which become their
         first estimates (slam_ekf_fej_augment).  With ``grow=True`` on the state both move into a larger handle when needed."""
@@ -1346,12 +1388,12 @@ class FirstEstimates:
             rc = self._lib.slam_ekf_fej_augment(self._f, _ptr(zp), zp.shape[0], _ptr(r))
         check(rc)
 
-    def observe(self, z, R, gate1, gate2):
-        """The product's association at the current estimates (``state.associate_vector``), then this update and this
-        add_features.  Returns the association vector."""
+    def observe(self, z, R, gate1, gate2, joint=False):
+        """The product's association at the current estimates (``state.associate_vector``), then this update -- with ``joint``
+        :meth:`update_joint` -- and this add_features.  Returns the association vector."""
         z = np.asarray(z, dtype=np.float64).reshape(2, -1)
         assoc = self.state.associate_vector(z, R, gate1, gate2)
-        self.update(z[:, assoc > 0], R, assoc[assoc > 0])
+        (self.update_joint if joint else self.update)(z[:, assoc > 0], R, assoc[assoc > 0])
         self.add_features(z[:, assoc < 0], R)
         return assoc
 

@@ -172,7 +172,7 @@ def default_QR():
 def sim(filt, waypoints: np.ndarray, landmarks: np.ndarray, seed: int, nlaps: int = 2,
         max_steps: int = 100000, monitor=None, fused: bool = False, prune_after=None, merge_gate=None,
         submap_steps=None, association: str = "nearest", nees_every=None, fix_every: int = 0,
-        fix_sigma: float = 0.5, local_radius=None, iterated=None, fej: bool = False) -> SimLog:
+        fix_sigma: float = 0.5, local_radius=None, iterated=None, fej: bool = False, fej_joint: bool = False) -> SimLog:
     """The loop of sim/ekfslam-sim.jl:80-141 without sleep/pause.
 
     ``filt`` must already hold the initial state (x = initial pose, P = 0).
@@ -222,7 +222,11 @@ def sim(filt, waypoints: np.ndarray, landmarks: np.ndarray, seed: int, nlaps: in
     add_features go through ``filt.fej()`` -- the Jacobians evaluated at every landmark's first estimate and at the predicted pose,
     the association at the current estimates as before; with ``fused`` the observation step is that object's ``observe`` (joint
     association: the three calls, fused or not).  Not available with ``submap_steps``, ``local_radius``, ``iterated``, ``prune_after`` or ``merge_gate``.
+    ``fej_joint``: False (default) changes nothing.  True, only with ``fej``: the step's update is that object's ``update_joint`` --
+    all matched observations of the step in one update (consecutive batches of 64) -- where ``update`` chains batches of 8.
     """
+    if fej_joint and not fej:
+        raise ValueError("fej_joint needs fej=True")
     if fej and (submap_steps is not None or local_radius is not None or iterated is not None or prune_after is not None
                 or merge_gate is not None):
         raise ValueError("fej is not available with submap_steps, local_radius, iterated, prune_after or merge_gate")
@@ -280,7 +284,8 @@ def sim(filt, waypoints: np.ndarray, landmarks: np.ndarray, seed: int, nlaps: in
                 if iterated is not None:
                     assoc = np.asarray(filt.observe_iterated(z, R, GATE1, GATE2, max_iter=iterated)[0])
                 else:
-                    assoc = np.asarray(filt.observe_joint(z, R, GATE1, GATE2)[0] if joint else step.observe(z, R, GATE1, GATE2))   # :114-120 in one call
+                    assoc = np.asarray(filt.observe_joint(z, R, GATE1, GATE2)[0] if joint else
+                                       (step.observe(z, R, GATE1, GATE2, joint=True) if fej_joint else step.observe(z, R, GATE1, GATE2)))   # :114-120 in one call
                 idf = assoc[assoc > 0]
                 zn = np.asarray(z, dtype=float).reshape(2, -1)[:, assoc < 0]
             else:
@@ -288,7 +293,7 @@ def sim(filt, waypoints: np.ndarray, landmarks: np.ndarray, seed: int, nlaps: in
                 if iterated is not None:
                     filt.update_iterated(zf, R, idf, max_iter=iterated)
                 else:
-                    step.update(zf, R, idf)                               # :117
+                    (step.update_joint if fej_joint else step.update)(zf, R, idf)     # :117
                 step.add_features(zn, R)                                  # :120
             log.obs_steps.append(nsteps)
             log.observations.append(np.array(z))
