@@ -166,20 +166,26 @@ for _name, (_res, _args) in SIGNATURES.items():
     _fn.argtypes = _args
 
 
-# ---- the companion libraries ------------------------------------------------------------------------------------------------
-# libslamhip.so exports exactly what its two headers declare; every later feature lives beside it in a companion library
-# libslamhip_<name>.so, which links against libslamhip.so (run path $ORIGIN), works on its handles and exports what
-# include/slamhip_<name>.h declares.  A companion is opened at its first use, not at import: a tree with only libslamhip.so
-# built imports and runs as before.
+# ---- the side libraries -----------------------------------------------------------------------------------------------------
+# libslamhip.so exports exactly what its two headers declare; every later feature lives beside it in a side library
+# libslamhip_<name>.so, which links against libslamhip.so (run path $ORIGIN), works on its handles and exports what its header
+# declares: include/slamhip_<name>.h for a companion, include/ext/slamhip_<name>.h for an extension (ext=True).  Each is one
+# Companion below and one row of LIBRARIES at the end of this section.  A side library is opened at its first use, not at
+# import: a tree with only libslamhip.so built imports and runs as before.
 class Companion:
     """libslamhip_<name>.so beside the package and its signature table; calling it returns the library, opened on first use.
+    `header` is its public header relative to the repository (under include/ext/ when `ext`), `libs` the other side libraries it
+    is linked against (<name>_LIBS in csrc/Makefile).
     No fallback: missing or unloadable is an ImportError.  With SLAMHIP_LIBRARY pointing elsewhere the handles belong to THAT
     library while the companion is linked against libslamhip.so, whose copy of the helpers it would run on them: refused."""
 
-    def __init__(self, name, signatures):
+    def __init__(self, name, signatures, ext=False, libs=()):
         self.name = name
         self.path = os.path.join(_HERE, f"libslamhip_{name}.so")
         self.signatures = signatures
+        self.ext = ext
+        self.libs = tuple(libs)
+        self.header = f"include/ext/slamhip_{name}.h" if ext else f"include/slamhip_{name}.h"
         self._lib = None
 
     def __call__(self):
@@ -313,9 +319,6 @@ PFCOPY_SIGNATURES = {
 pfcopy_lib = Companion("pfcopy", PFCOPY_SIGNATURES)
 PFCOPY_LIB_PATH = pfcopy_lib.path
 
-#: companion name -> its loader, in the order the libraries were added
-COMPANIONS = {c.name: c for c in (frame_lib, join_lib, evidence_lib, jc_lib, path_lib, copy_lib, handover_lib, pfcopy_lib)}
-
 # ---- the extensions: libraries wired like a companion whose header lives in include/ext/ ------------------------------------
 # ---- factor: the Cholesky factor of an EKF state's covariance, opened when the first factor object is made --------------------
 SLAM_FACTOR_MAXRHS = 64
@@ -332,16 +335,10 @@ FACTOR_SIGNATURES = {
     "slam_ekf_factor_multiply": (C.c_int, [_h, _dp, C.c_int, C.c_int, _dp]),
 }
 
-factor_lib = Companion("factor", FACTOR_SIGNATURES)
+factor_lib = Companion("factor", FACTOR_SIGNATURES, ext=True)
 FACTOR_LIB_PATH = factor_lib.path
 
-#: extension name -> its loader
-EXTENSIONS = {"factor": factor_lib}
-
 # ---- linear: caller-supplied motion and measurement models for the EKF, opened at the first such call --------------------------
-# Wired like factor (the same Makefile rule, the same loader class, the header in include/ext/), but entered in NEITHER table:
-# tests/test_companions_cpu.py and tests/test_factor_ref_cpu.py pin COMPANIONS and EXTENSIONS as they stand, and the surface
-# checks those tables drive are made for this library by tests/test_linear_ref_cpu.py.
 SLAM_LINEAR_MAXROWS = 16
 SLAM_LINEAR_MAXNNZ = 8
 SLAM_LINEAR_MEASURED, SLAM_LINEAR_INNOVATION = 0, 1
@@ -354,11 +351,10 @@ LINEAR_SIGNATURES = {
     "slam_ekf_predict_odometry": (C.c_int, [_h, _dp, _dp]),
 }
 
-linear_lib = Companion("linear", LINEAR_SIGNATURES)
+linear_lib = Companion("linear", LINEAR_SIGNATURES, ext=True)
 LINEAR_LIB_PATH = linear_lib.path
 
 # ---- proposal: FastSLAM 2.0 with unknown correspondences, opened at the first such step -------------------------------------------
-# Wired like linear, and like it entered in neither table; its surface checks are made by tests/test_proposal_unknown_ref_cpu.py.
 #: every symbol include/ext/slamhip_proposal.h declares
 PROPOSAL_SIGNATURES = {
     "slam_pf_step_proposal_unknown": (C.c_int, [_h, C.c_double, C.c_double, C.c_double, _dp, C.c_double, _dp, C.c_int, _dp,
@@ -368,12 +364,11 @@ PROPOSAL_SIGNATURES = {
     "slam_pf_proposal_limits": (C.c_int, [C.POINTER(C.c_int)]),
 }
 
-proposal_lib = Companion("proposal", PROPOSAL_SIGNATURES)
+proposal_lib = Companion("proposal", PROPOSAL_SIGNATURES, ext=True)
 PROPOSAL_LIB_PATH = proposal_lib.path
 
 
 # ---- local: compressed local-area updates for the EKF, opened when the first area object is made ----------------------------------
-# Wired like linear, and like it entered in neither table; its surface checks are made by tests/test_local_ref_cpu.py.
 SLAM_LOCAL_MAXLM = 1024
 
 #: every symbol include/ext/slamhip_local.h declares
@@ -391,12 +386,11 @@ LOCAL_SIGNATURES = {
     "slam_ekf_local_get": (C.c_int, [_h, _dp, _dp, _dp]),
 }
 
-local_lib = Companion("local", LOCAL_SIGNATURES)
+local_lib = Companion("local", LOCAL_SIGNATURES, ext=True, libs=("copy",))
 LOCAL_LIB_PATH = local_lib.path
 
 
 # ---- iterated: the iterated EKF update, relinearised on the device, opened at the first such call ----------------------------------
-# Wired like linear, and like it entered in neither table; its surface checks are made by tests/test_iterated_ref_cpu.py.
 SLAM_ITERATED_MAXOBS = 8
 SLAM_ITERATED_MAXITER = 64
 
@@ -407,12 +401,11 @@ ITERATED_SIGNATURES = {
     "slam_ekf_iterated_limits": (C.c_int, [_ip]),
 }
 
-iterated_lib = Companion("iterated", ITERATED_SIGNATURES)
+iterated_lib = Companion("iterated", ITERATED_SIGNATURES, ext=True)
 ITERATED_LIB_PATH = iterated_lib.path
 
 
 # ---- fej: first-estimates Jacobian predict, update and augment for the EKF, opened when the first such object is made ---------------
-# Wired like iterated, and like it entered in neither table; its surface checks are made by tests/test_fej_ref_cpu.py.
 SLAM_FEJ_MAXOBS = 8
 
 #: every symbol include/ext/slamhip_fej.h declares
@@ -430,12 +423,11 @@ FEJ_SIGNATURES = {
     "slam_ekf_fej_limits": (C.c_int, [_ip]),
 }
 
-fej_lib = Companion("fej", FEJ_SIGNATURES)
+fej_lib = Companion("fej", FEJ_SIGNATURES, ext=True)
 FEJ_LIB_PATH = fej_lib.path
 
 
 # ---- wide: the joint update of up to 64 observations in one down-date, opened at the first such call --------------------------------
-# Wired like fej, and like it entered in neither table; its surface checks are made by tests/test_wide_ref_cpu.py.
 SLAM_WIDE_MAXOBS = 64
 
 #: every symbol include/ext/slamhip_wide.h declares
@@ -445,8 +437,16 @@ WIDE_SIGNATURES = {
     "slam_ekf_wide_limits": (C.c_int, [_ip]),
 }
 
-wide_lib = Companion("wide", WIDE_SIGNATURES)
+wide_lib = Companion("wide", WIDE_SIGNATURES, ext=True)
 WIDE_LIB_PATH = wide_lib.path
+
+#: side library name -> its loader, all fifteen in the order they were added.  A new library is one row here.
+LIBRARIES = {c.name: c for c in (frame_lib, join_lib, evidence_lib, jc_lib, path_lib, copy_lib, handover_lib, pfcopy_lib,
+                                 factor_lib, linear_lib, proposal_lib, local_lib, iterated_lib, fej_lib, wide_lib)}
+#: the rows whose header lies in include/
+COMPANIONS = {name: c for name, c in LIBRARIES.items() if not c.ext}
+#: the rows whose header lies in include/ext/
+EXTENSIONS = {name: c for name, c in LIBRARIES.items() if c.ext}
 
 
 def proposal_max_obs() -> int:

@@ -1,14 +1,9 @@
 """The covariance factor (slam_ekf_factor_*, include/ext/slamhip_factor.h), the parts that need no GPU: tests/factor_ref.py against
 numpy.linalg.cholesky and LAPACK's potrf (factor, first failing index), what the entrywise bound catches on a model with a defect
-injected, and the surface checks tests/test_companions_cpu.py makes for the eight companions, here for the extension library:
-header == ctypes table == exports == Julia ccalls, how it finds the product library, disjoint export sets, null-handle status
-codes and the loader's two refusals."""
+injected, what is particular to this library's surface (the checks every side library shares are made from its row of the table
+by tests/test_companions_cpu.py) and the null-handle status codes."""
 import ctypes
-import glob
 import os
-import shutil
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -103,52 +98,12 @@ def test_the_entrywise_bound_catches_a_dropped_tile_product_and_bf16_operands():
     assert idx == -1 and FR.factor_ratio(bad, P, "f32")[0] > 100.0
 
 
-# ---- the surface ---------------------------------------------------------------------------------------------------------------------
-def test_header_ctypes_library_and_julia_name_the_same_surface(pkg):
+# ---- the surface: the checks every library shares are tests/test_companions_cpu.py's, from this library's row of the table --------
+def test_what_is_particular_to_this_library(pkg):
     L = pkg._lib
-    loader = L.factor_lib
-    sigs = L.FACTOR_SIGNATURES
-    assert loader.signatures is sigs and loader.name == "factor"
-    assert loader.path == L.FACTOR_LIB_PATH == os.path.join(os.path.dirname(L.LIB_PATH), "libslamhip_factor.so")
-    names = ABI.declared(HEADER)
-    assert names == NAMES == set(sigs) == ABI.exported(loader.path), (names, set(sigs), ABI.exported(loader.path))
-    protos = ABI.prototypes(HEADER)
-    assert set(protos) == names
-    for sym, (res, args) in sigs.items():
-        assert protos[sym] == len(args), (sym, protos[sym], len(args))
-        assert res is ctypes.c_int, sym
-    needed = ABI.dynamic_section(loader.path)
-    assert "libslamhip.so" in needed and "$ORIGIN" in needed
-    ldd = subprocess.run(["ldd", loader.path], capture_output=True, text=True).stdout
-    assert "libslamhip.so" in ldd and "torch" not in ldd and "python" not in ldd
-    lib = loader()
-    assert lib is loader() and all(getattr(lib, sym).argtypes == args for sym, (_res, args) in sigs.items())
-    calls = ABI.julia_ccalls("libslamhip_factor")
-    assert {c[0] for c in calls} == names
-    for sym, ret, nargs in calls:
-        assert ret == "Cint" and nargs == len(sigs[sym][1]), (sym, ret, nargs, len(sigs[sym][1]))
-    with open(ABI.JULIA) as f:
-        src = f.read()
-    for sym in names:
-        assert f"(:{sym}, libslamhip_factor)" in src
-    assert "SLAMHIP_FACTOR_LIB" in src
+    assert NAMES == set(L.factor_lib.signatures)
     with open(HEADER) as f:
         assert '#include "slamhip.h"' in f.read()
-
-
-def test_the_tables_and_the_export_sets(pkg):
-    L = pkg._lib
-    assert list(L.COMPANIONS) == ["frame", "join", "evidence", "jc", "path", "copy", "handover", "pfcopy"]
-    assert list(L.EXTENSIONS) == ["factor"] and L.EXTENSIONS["factor"] is L.factor_lib
-    mine = ABI.exported(L.FACTOR_LIB_PATH)
-    assert mine == NAMES
-    assert not mine & ABI.exported(L.LIB_PATH)
-    assert not NAMES & set(L.SIGNATURES)
-    for name, c in L.COMPANIONS.items():
-        assert not mine & ABI.exported(c.path), name
-        assert not NAMES & set(c.signatures), name
-    # the header lies outside the glob that pins the top-level headers
-    assert os.path.join(ABI.INCLUDE, "ext", "slamhip_factor.h") not in glob.glob(os.path.join(ABI.INCLUDE, "slamhip*.h"))
 
 
 def test_null_handles_and_bad_arguments_are_status_codes(pkg):
@@ -173,63 +128,3 @@ def test_null_handles_and_bad_arguments_are_status_codes(pkg):
     assert lib.slam_ekf_factor_mean(None, buf) == BAD
     assert lib.slam_ekf_factor_solve(None, buf, 1, 8, buf, buf) == BAD
     assert lib.slam_ekf_factor_multiply(None, buf, 1, 8, buf) == BAD
-
-
-REFUSAL = """
-import os, sys
-sys.path.insert(0, {root!r})
-from __graft_entry__ import load_package
-L = load_package()._lib
-assert L.LIB_PATH == os.environ["SLAMHIP_LIBRARY"]
-own = os.path.join(os.path.dirname(os.path.abspath(L.__file__)), "libslamhip.so")
-try:
-    L.factor_lib()
-except ImportError as e:
-    for word in ("libslamhip_factor.so", own, L.LIB_PATH, "SLAMHIP_LIBRARY"):
-        assert word in str(e), (word, str(e))
-else:
-    raise SystemExit("opened although the handles belong to another library")
-print("refused")
-"""
-
-MISSING = """
-import importlib.util, os, sys
-d = {copy!r}
-spec = importlib.util.spec_from_file_location("slam_copy_without_extensions", os.path.join(d, "__init__.py"), submodule_search_locations=[d])
-mod = importlib.util.module_from_spec(spec)
-sys.modules[spec.name] = mod
-spec.loader.exec_module(mod)
-L = mod._lib
-loader = L.EXTENSIONS["factor"]
-assert loader.path == os.path.join(d, "libslamhip_factor.so") and not os.path.exists(loader.path)
-try:
-    loader()
-except ImportError as e:
-    for word in (loader.path, "is missing", "make -C slam.jl_amd/csrc"):
-        assert word in str(e), (word, str(e))
-else:
-    raise SystemExit("opened although it is not there")
-print("missing")
-"""
-
-
-def _child(script, env):
-    res = subprocess.run([sys.executable, "-c", script], capture_output=True, text=True, timeout=300, env=env)
-    assert res.returncode == 0, res.stdout + res.stderr
-    return res.stdout.split()
-
-
-def test_the_loader_refuses_a_foreign_product_library(pkg, tmp_path):
-    foreign = str(tmp_path / "libslamhip.so")
-    shutil.copy(pkg._lib.LIB_PATH, foreign)
-    assert _child(REFUSAL.format(root=ABI.ROOT), dict(os.environ, SLAMHIP_LIBRARY=foreign)) == ["refused"]
-
-
-def test_the_loader_names_the_build_command_when_the_library_was_not_built(pkg, tmp_path):
-    copy = tmp_path / "pkg"
-    copy.mkdir()
-    pkgdir = os.path.dirname(os.path.abspath(pkg._lib.__file__))
-    for path in glob.glob(os.path.join(pkgdir, "*.py")) + [os.path.join(pkgdir, "libslamhip.so")]:
-        shutil.copy(path, str(copy))
-    env = {k: v for k, v in os.environ.items() if k != "SLAMHIP_LIBRARY"}
-    assert _child(MISSING.format(copy=str(copy)), env) == ["missing"]

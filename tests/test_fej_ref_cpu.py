@@ -1,20 +1,16 @@
 """First-estimates Jacobian predict, update and augment (libslamhip_fej.so, include/ext/slamhip_fej.h), the parts that need no GPU:
 tests/fej_ref.py against the oracle (its twin, with the linearisation points re-set before every call, IS the oracle's filter);
 the observability argument the rule rests on -- H N = 0 at every update, N' inv(P) N constant without process noise, neither of
-which the standard filter keeps --; remap / reset / transform on the reference; and the surface checks tests/test_iterated_ref_cpu.py
-makes for its library, here for this one.
+which the standard filter keeps --; remap / reset / transform on the reference; and what is particular to this library's surface
+(the checks every side library shares are made from its row of the table by tests/test_companions_cpu.py).
 
 The bars of the first three tests are the ones the rule was prototyped against: 1e-12 where fp64 rounding alone separates two
 quantities (measured 2e-13, 7e-15), 1e-9 for the drift of N' inv(P) N, which passes through inv(P) with cond(P) ~ 3e7 (measured
 4e-14), and 0.1 / 1 for the standard filter's violations, which are of order one (measured 0.72 .. 1.5 and 2.6 .. 12)."""
 import ctypes
-import glob
 import inspect
 import math
 import os
-import shutil
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -178,35 +174,13 @@ def test_batches_keep_the_jacobians_and_move_the_residuals():
 
 
 # ---- 5. the surface -----------------------------------------------------------------------------------------------------------------
-def test_header_ctypes_library_and_julia_name_the_same_surface(pkg):
+def test_what_is_particular_to_this_library(pkg):
+    """The checks every library shares are tests/test_companions_cpu.py's, from this library's row of the table."""
     L = pkg._lib
-    loader = L.fej_lib
-    sigs = L.FEJ_SIGNATURES
-    assert loader.signatures is sigs and loader.name == "fej"
-    assert loader.path == L.FEJ_LIB_PATH == os.path.join(os.path.dirname(L.LIB_PATH), "libslamhip_fej.so")
-    names = ABI.declared(HEADER)
     assert len(NAMES) == 11
-    assert names == NAMES == set(sigs) == ABI.exported(loader.path), (names, set(sigs), ABI.exported(loader.path))
-    protos = ABI.prototypes(HEADER)
-    assert set(protos) == names
-    for sym, (res, args) in sigs.items():
-        assert protos[sym] == len(args), (sym, protos[sym], len(args))
-        assert res is ctypes.c_int, sym
-    needed = ABI.dynamic_section(loader.path)
-    assert "libslamhip.so" in needed and "$ORIGIN" in needed
-    ldd = subprocess.run(["ldd", loader.path], capture_output=True, text=True).stdout
-    assert "libslamhip.so" in ldd and "torch" not in ldd and "python" not in ldd
-    lib = loader()
-    assert lib is loader() and all(getattr(lib, sym).argtypes == args for sym, (_res, args) in sigs.items())
-    calls = ABI.julia_ccalls("libslamhip_fej")
-    assert {c[0] for c in calls} == names
-    for sym, ret, nargs in calls:
-        assert ret == "Cint" and nargs == len(sigs[sym][1]), (sym, ret, nargs, len(sigs[sym][1]))
+    assert NAMES == set(L.fej_lib.signatures)
     with open(ABI.JULIA) as f:
         src = f.read()
-    for sym in names:
-        assert f"(:{sym}, libslamhip_fej)" in src
-    assert "SLAMHIP_FEJ_LIB" in src
     for word in ("FirstEstimates", "fej", "remap!", "reset!"):
         assert word in src.split("module SLAMHip")[1].split("const libslamhip =")[0], word      # exported
     with open(HEADER) as f:
@@ -214,27 +188,7 @@ def test_header_ctypes_library_and_julia_name_the_same_surface(pkg):
     assert '#include "slamhip.h"' in text
     assert L.SLAM_FEJ_MAXOBS == 8 == F.MAXOBS == L.SLAM_ITERATED_MAXOBS and "#define SLAM_FEJ_MAXOBS 8" in text
     lim = (ctypes.c_int32 * 1)()
-    assert lib.slam_ekf_fej_limits(lim) == L.SLAM_OK and list(lim) == [8]      # (touches no device)
-
-
-def test_the_tables_are_unchanged_and_the_export_sets_disjoint(pkg):
-    L = pkg._lib
-    assert list(L.COMPANIONS) == ["frame", "join", "evidence", "jc", "path", "copy", "handover", "pfcopy"]
-    assert list(L.EXTENSIONS) == ["factor"]
-    assert L.fej_lib not in list(L.COMPANIONS.values()) + list(L.EXTENSIONS.values())
-    mine = ABI.exported(L.FEJ_LIB_PATH)
-    assert mine == NAMES
-    assert not mine & ABI.exported(L.LIB_PATH)
-    assert not NAMES & set(L.SIGNATURES)
-    # libslamhip.so exports what its two headers declare, no more: this library added nothing to it
-    product = ABI.declared(os.path.join(ABI.INCLUDE, "slamhip.h")) | ABI.declared(os.path.join(ABI.INCLUDE, "slamhip_diag.h"))
-    assert ABI.exported(L.LIB_PATH) == product == set(L.SIGNATURES)
-    others = [("linear", L.linear_lib), ("proposal", L.proposal_lib), ("local", L.local_lib), ("iterated", L.iterated_lib)]
-    for name, c in list(L.COMPANIONS.items()) + list(L.EXTENSIONS.items()) + others:
-        assert not mine & ABI.exported(c.path), name
-        assert not NAMES & set(c.signatures), name
-    assert ABI.exported(L.ITERATED_LIB_PATH) == set(L.ITERATED_SIGNATURES)       # the shared panel kernel added no export there
-    assert HEADER not in glob.glob(os.path.join(ABI.INCLUDE, "slamhip*.h"))
+    assert L.fej_lib().slam_ekf_fej_limits(lim) == L.SLAM_OK and list(lim) == [8]      # (touches no device)
     assert callable(pkg.EKFSlamState.fej) and pkg.FirstEstimates is pkg.ekf.FirstEstimates
     for word in ("predict", "update", "add_features", "observe", "reset", "remap", "transform", "get", "set", "close"):
         assert callable(getattr(pkg.FirstEstimates, word)), word
@@ -298,62 +252,3 @@ def test_bad_arguments_are_status_codes_without_a_device(pkg):
     assert lib.slam_ekf_fej_create(ctypes.byref(made), None) == BAD and not made.value      # nothing is handed out
     assert lib.slam_ekf_fej_destroy(None) == L.SLAM_OK
     assert lib.slam_ekf_fej_limits(None) == BAD
-
-
-REFUSAL = """
-import os, sys
-sys.path.insert(0, {root!r})
-from __graft_entry__ import load_package
-L = load_package()._lib
-assert L.LIB_PATH == os.environ["SLAMHIP_LIBRARY"]
-own = os.path.join(os.path.dirname(os.path.abspath(L.__file__)), "libslamhip.so")
-try:
-    L.fej_lib()
-except ImportError as e:
-    for word in ("libslamhip_fej.so", own, L.LIB_PATH, "SLAMHIP_LIBRARY"):
-        assert word in str(e), (word, str(e))
-else:
-    raise SystemExit("opened although the handles belong to another library")
-print("refused")
-"""
-
-MISSING = """
-import importlib.util, os, sys
-d = {copy!r}
-spec = importlib.util.spec_from_file_location("slam_copy_without_fej", os.path.join(d, "__init__.py"), submodule_search_locations=[d])
-mod = importlib.util.module_from_spec(spec)
-sys.modules[spec.name] = mod
-spec.loader.exec_module(mod)
-loader = mod._lib.fej_lib
-assert loader.path == os.path.join(d, "libslamhip_fej.so") and not os.path.exists(loader.path)
-try:
-    loader()
-except ImportError as e:
-    for word in (loader.path, "is missing", "make -C slam.jl_amd/csrc"):
-        assert word in str(e), (word, str(e))
-else:
-    raise SystemExit("opened although it is not there")
-print("missing")
-"""
-
-
-def _child(script, env):
-    res = subprocess.run([sys.executable, "-c", script], capture_output=True, text=True, timeout=300, env=env)
-    assert res.returncode == 0, res.stdout + res.stderr
-    return res.stdout.split()
-
-
-def test_the_loader_refuses_a_foreign_product_library(pkg, tmp_path):
-    foreign = str(tmp_path / "libslamhip.so")
-    shutil.copy(pkg._lib.LIB_PATH, foreign)
-    assert _child(REFUSAL.format(root=ABI.ROOT), dict(os.environ, SLAMHIP_LIBRARY=foreign)) == ["refused"]
-
-
-def test_the_loader_names_the_build_command_when_the_library_was_not_built(pkg, tmp_path):
-    copy = tmp_path / "pkg"
-    copy.mkdir()
-    pkgdir = os.path.dirname(os.path.abspath(pkg._lib.__file__))
-    for path in glob.glob(os.path.join(pkgdir, "*.py")) + [os.path.join(pkgdir, "libslamhip.so")]:
-        shutil.copy(path, str(copy))
-    env = {k: v for k, v in os.environ.items() if k != "SLAMHIP_LIBRARY"}
-    assert _child(MISSING.format(copy=str(copy)), env) == ["missing"]

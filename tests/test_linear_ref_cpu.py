@@ -1,15 +1,10 @@
 """Caller-supplied models for the EKF (slam_ekf_update_linear / linear_nis / predict_linear / predict_odometry,
 include/ext/slamhip_linear.h), the parts that need no GPU: tests/linear_ref.py against the oracle's update and predict,
-tests/merge_ref.py and hand-derived answers; the surface checks tests/test_factor_ref_cpu.py makes for its extension library, here
-for this one (header == ctypes table == exports == Julia ccalls, how it finds the product library, disjoint export sets, the two
-loader tables unchanged, the loader's two refusals); and the status codes that are decided before a device is touched."""
+tests/merge_ref.py and hand-derived answers; what is particular to this library's surface (the checks every side library shares are
+made from its row of the table by tests/test_companions_cpu.py); and the status codes that are decided before a device is touched."""
 import ctypes
-import glob
 import math
 import os
-import shutil
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -153,35 +148,12 @@ def test_a_singular_s_is_reported_with_its_pivot_and_leaves_the_state():
     assert ptr.tolist() == [0, 2, 3] and idx.tolist() == [0, 7, 5] and val.tolist() == [1.0, 2.0, -1.0]
 
 
-# ---- the surface ----------------------------------------------------------------------------------------------------------------
-def test_header_ctypes_library_and_julia_name_the_same_surface(pkg):
+# ---- the surface: the checks every library shares are tests/test_companions_cpu.py's, from this library's row of the table --------
+def test_what_is_particular_to_this_library(pkg):
     L = pkg._lib
-    loader = L.linear_lib
-    sigs = L.LINEAR_SIGNATURES
-    assert loader.signatures is sigs and loader.name == "linear"
-    assert loader.path == L.LINEAR_LIB_PATH == os.path.join(os.path.dirname(L.LIB_PATH), "libslamhip_linear.so")
-    names = ABI.declared(HEADER)
-    assert names == NAMES == set(sigs) == ABI.exported(loader.path), (names, set(sigs), ABI.exported(loader.path))
-    protos = ABI.prototypes(HEADER)
-    assert set(protos) == names
-    for sym, (res, args) in sigs.items():
-        assert protos[sym] == len(args), (sym, protos[sym], len(args))
-        assert res is ctypes.c_int, sym
-    needed = ABI.dynamic_section(loader.path)
-    assert "libslamhip.so" in needed and "$ORIGIN" in needed
-    ldd = subprocess.run(["ldd", loader.path], capture_output=True, text=True).stdout
-    assert "libslamhip.so" in ldd and "torch" not in ldd and "python" not in ldd
-    lib = loader()
-    assert lib is loader() and all(getattr(lib, sym).argtypes == args for sym, (_res, args) in sigs.items())
-    calls = ABI.julia_ccalls("libslamhip_linear")
-    assert {c[0] for c in calls} == names
-    for sym, ret, nargs in calls:
-        assert ret == "Cint" and nargs == len(sigs[sym][1]), (sym, ret, nargs, len(sigs[sym][1]))
+    assert NAMES == set(L.linear_lib.signatures)
     with open(ABI.JULIA) as f:
         src = f.read()
-    for sym in names:
-        assert f"(:{sym}, libslamhip_linear)" in src
-    assert "SLAMHIP_LINEAR_LIB" in src
     for word in ("update_linear!", "linear_nis", "predict_linear!", "predict_odometry!", "fix_position!", "fix_heading!", "fix_landmark!"):
         assert word in src.split("module SLAMHip")[1].split("const libslamhip =")[0], word      # exported
     with open(HEADER) as f:
@@ -190,21 +162,6 @@ def test_header_ctypes_library_and_julia_name_the_same_surface(pkg):
     assert (L.SLAM_LINEAR_MAXROWS, L.SLAM_LINEAR_MAXNNZ) == (16, 8) == (LR.MAXROWS, LR.MAXNNZ)
     assert "#define SLAM_LINEAR_MAXROWS 16" in text and "#define SLAM_LINEAR_MAXNNZ 8" in text
     assert (L.SLAM_LINEAR_MEASURED, L.SLAM_LINEAR_INNOVATION) == (0, 1) == (LR.MEASURED, LR.INNOVATION)
-
-
-def test_the_tables_are_unchanged_and_the_export_sets_disjoint(pkg):
-    L = pkg._lib
-    assert list(L.COMPANIONS) == ["frame", "join", "evidence", "jc", "path", "copy", "handover", "pfcopy"]
-    assert list(L.EXTENSIONS) == ["factor"]
-    assert L.linear_lib not in list(L.COMPANIONS.values()) + list(L.EXTENSIONS.values())
-    mine = ABI.exported(L.LINEAR_LIB_PATH)
-    assert mine == NAMES
-    assert not mine & ABI.exported(L.LIB_PATH)
-    assert not NAMES & set(L.SIGNATURES)
-    for name, c in list(L.COMPANIONS.items()) + list(L.EXTENSIONS.items()):
-        assert not mine & ABI.exported(c.path), name
-        assert not NAMES & set(c.signatures), name
-    assert HEADER not in glob.glob(os.path.join(ABI.INCLUDE, "slamhip*.h"))
     for word in ("update_linear", "linear_nis", "predict_linear", "predict_odometry", "fix_position", "fix_heading", "fix_landmark",
                  "constrain_landmarks"):
         assert callable(getattr(pkg.EKFSlamState, word)), word
@@ -255,62 +212,3 @@ def test_linear_rows_takes_a_dense_matrix_or_a_list_of_rows(pkg):
     assert all(np.array_equal(a, b) for a, b in zip((ptr, idx, val), want))
     with pytest.raises(ValueError):
         pkg.ekf.linear_rows(np.zeros((2, 8)), 9)
-
-
-REFUSAL = """
-import os, sys
-sys.path.insert(0, {root!r})
-from __graft_entry__ import load_package
-L = load_package()._lib
-assert L.LIB_PATH == os.environ["SLAMHIP_LIBRARY"]
-own = os.path.join(os.path.dirname(os.path.abspath(L.__file__)), "libslamhip.so")
-try:
-    L.linear_lib()
-except ImportError as e:
-    for word in ("libslamhip_linear.so", own, L.LIB_PATH, "SLAMHIP_LIBRARY"):
-        assert word in str(e), (word, str(e))
-else:
-    raise SystemExit("opened although the handles belong to another library")
-print("refused")
-"""
-
-MISSING = """
-import importlib.util, os, sys
-d = {copy!r}
-spec = importlib.util.spec_from_file_location("slam_copy_without_linear", os.path.join(d, "__init__.py"), submodule_search_locations=[d])
-mod = importlib.util.module_from_spec(spec)
-sys.modules[spec.name] = mod
-spec.loader.exec_module(mod)
-loader = mod._lib.linear_lib
-assert loader.path == os.path.join(d, "libslamhip_linear.so") and not os.path.exists(loader.path)
-try:
-    loader()
-except ImportError as e:
-    for word in (loader.path, "is missing", "make -C slam.jl_amd/csrc"):
-        assert word in str(e), (word, str(e))
-else:
-    raise SystemExit("opened although it is not there")
-print("missing")
-"""
-
-
-def _child(script, env):
-    res = subprocess.run([sys.executable, "-c", script], capture_output=True, text=True, timeout=300, env=env)
-    assert res.returncode == 0, res.stdout + res.stderr
-    return res.stdout.split()
-
-
-def test_the_loader_refuses_a_foreign_product_library(pkg, tmp_path):
-    foreign = str(tmp_path / "libslamhip.so")
-    shutil.copy(pkg._lib.LIB_PATH, foreign)
-    assert _child(REFUSAL.format(root=ABI.ROOT), dict(os.environ, SLAMHIP_LIBRARY=foreign)) == ["refused"]
-
-
-def test_the_loader_names_the_build_command_when_the_library_was_not_built(pkg, tmp_path):
-    copy = tmp_path / "pkg"
-    copy.mkdir()
-    pkgdir = os.path.dirname(os.path.abspath(pkg._lib.__file__))
-    for path in glob.glob(os.path.join(pkgdir, "*.py")) + [os.path.join(pkgdir, "libslamhip.so")]:
-        shutil.copy(path, str(copy))
-    env = {k: v for k, v in os.environ.items() if k != "SLAMHIP_LIBRARY"}
-    assert _child(MISSING.format(copy=str(copy)), env) == ["missing"]

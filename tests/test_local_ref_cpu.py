@@ -1,14 +1,10 @@
 """Compressed local-area updates (slam_ekf_local_*, include/ext/slamhip_local.h), the parts that need no GPU: tests/local_ref.py
-against the oracle's full filter, and the surface checks tests/test_linear_ref_cpu.py makes for its library, here for this one
-(header == ctypes table == exports == Julia ccalls, how it finds its neighbours, disjoint export sets, the two loader tables
-unchanged, the loader's two refusals, the status codes decided before a device is touched)."""
+against the oracle's full filter, what is particular to this library's surface (the checks every side library shares are made from
+its row of the table by tests/test_companions_cpu.py), and the status codes decided before a device is touched."""
 import ctypes
-import glob
+import inspect
 import math
 import os
-import shutil
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -138,61 +134,22 @@ def test_the_bound_of_close_holds_for_a_rounded_model_of_it():
     assert np.any(np.abs(Pm - Pe) > BP)
 
 
-# ---- the surface ----------------------------------------------------------------------------------------------------------------
-def test_header_ctypes_library_and_julia_name_the_same_surface(pkg):
+# ---- the surface: the checks every library shares are tests/test_companions_cpu.py's, from this library's row of the table --------
+def test_what_is_particular_to_this_library(pkg):
     L = pkg._lib
-    loader = L.local_lib
-    sigs = L.LOCAL_SIGNATURES
-    assert loader.signatures is sigs and loader.name == "local"
-    assert loader.path == L.LOCAL_LIB_PATH == os.path.join(os.path.dirname(L.LIB_PATH), "libslamhip_local.so")
-    names = ABI.declared(HEADER)
-    assert names == NAMES == set(sigs) == ABI.exported(loader.path), (names, set(sigs), ABI.exported(loader.path))
-    protos = ABI.prototypes(HEADER)
-    assert set(protos) == names
-    for sym, (res, args) in sigs.items():
-        assert protos[sym] == len(args), (sym, protos[sym], len(args))
-        assert res is ctypes.c_int, sym
-    needed = ABI.dynamic_section(loader.path)
-    assert "libslamhip.so" in needed and "libslamhip_copy.so" in needed and "$ORIGIN" in needed
-    ldd = subprocess.run(["ldd", loader.path], capture_output=True, text=True).stdout
-    assert "libslamhip.so" in ldd and "libslamhip_copy.so" in ldd and "torch" not in ldd and "python" not in ldd
-    lib = loader()
-    assert lib is loader() and all(getattr(lib, sym).argtypes == args for sym, (_res, args) in sigs.items())
-    calls = ABI.julia_ccalls("libslamhip_local")
-    assert {c[0] for c in calls} == names
-    for sym, ret, nargs in calls:
-        assert ret == "Cint" and nargs == len(sigs[sym][1]), (sym, ret, nargs, len(sigs[sym][1]))
+    assert NAMES == set(L.local_lib.signatures)
     with open(ABI.JULIA) as f:
         src = f.read()
-    for sym in names:
-        assert f"(:{sym}, libslamhip_local)" in src
-    assert "SLAMHIP_LOCAL_LIB" in src
     for word in ("LocalArea", "open_area!", "close!", "abort!", "landmarks_within"):
         assert word in src.split("module SLAMHip")[1].split("const libslamhip =")[0], word      # exported
     with open(HEADER) as f:
         text = f.read()
     assert '#include "slamhip.h"' in text
     assert L.SLAM_LOCAL_MAXLM == 1024 == LF.MAXLM and "#define SLAM_LOCAL_MAXLM 1024" in text
-
-
-def test_the_tables_are_unchanged_and_the_export_sets_disjoint(pkg):
-    L = pkg._lib
-    assert list(L.COMPANIONS) == ["frame", "join", "evidence", "jc", "path", "copy", "handover", "pfcopy"]
-    assert list(L.EXTENSIONS) == ["factor"]
-    assert L.local_lib not in list(L.COMPANIONS.values()) + list(L.EXTENSIONS.values())
-    mine = ABI.exported(L.LOCAL_LIB_PATH)
-    assert mine == NAMES
-    assert not mine & ABI.exported(L.LIB_PATH)
-    assert not NAMES & set(L.SIGNATURES)
-    for name, c in list(L.COMPANIONS.items()) + list(L.EXTENSIONS.items()) + [("linear", L.linear_lib), ("proposal", L.proposal_lib)]:
-        assert not mine & ABI.exported(c.path), name
-        assert not NAMES & set(c.signatures), name
-    assert HEADER not in glob.glob(os.path.join(ABI.INCLUDE, "slamhip*.h"))
     for word in ("local", "landmarks_within"):
         assert callable(getattr(pkg.EKFSlamState, word)), word
     for word in ("predict", "update", "add_features", "associate", "observe", "close", "abort", "accumulators"):
         assert callable(getattr(pkg.LocalArea, word)), word
-    import inspect
     assert inspect.signature(pkg.sim.sim).parameters["local_radius"].default is None
 
 
@@ -223,62 +180,3 @@ def test_bad_arguments_are_status_codes_without_a_device(pkg):
     assert lib.slam_ekf_local_info(None, i64) == BAD
     assert lib.slam_ekf_local_get(None, dbl, dbl, dbl) == BAD
     assert lib.slam_ekf_local_destroy(None) == L.SLAM_OK
-
-
-REFUSAL = """
-import os, sys
-sys.path.insert(0, {root!r})
-from __graft_entry__ import load_package
-L = load_package()._lib
-assert L.LIB_PATH == os.environ["SLAMHIP_LIBRARY"]
-own = os.path.join(os.path.dirname(os.path.abspath(L.__file__)), "libslamhip.so")
-try:
-    L.local_lib()
-except ImportError as e:
-    for word in ("libslamhip_local.so", own, L.LIB_PATH, "SLAMHIP_LIBRARY"):
-        assert word in str(e), (word, str(e))
-else:
-    raise SystemExit("opened although the handles belong to another library")
-print("refused")
-"""
-
-MISSING = """
-import importlib.util, os, sys
-d = {copy!r}
-spec = importlib.util.spec_from_file_location("slam_copy_without_local", os.path.join(d, "__init__.py"), submodule_search_locations=[d])
-mod = importlib.util.module_from_spec(spec)
-sys.modules[spec.name] = mod
-spec.loader.exec_module(mod)
-loader = mod._lib.local_lib
-assert loader.path == os.path.join(d, "libslamhip_local.so") and not os.path.exists(loader.path)
-try:
-    loader()
-except ImportError as e:
-    for word in (loader.path, "is missing", "make -C slam.jl_amd/csrc"):
-        assert word in str(e), (word, str(e))
-else:
-    raise SystemExit("opened although it is not there")
-print("missing")
-"""
-
-
-def _child(script, env):
-    res = subprocess.run([sys.executable, "-c", script], capture_output=True, text=True, timeout=300, env=env)
-    assert res.returncode == 0, res.stdout + res.stderr
-    return res.stdout.split()
-
-
-def test_the_loader_refuses_a_foreign_product_library(pkg, tmp_path):
-    foreign = str(tmp_path / "libslamhip.so")
-    shutil.copy(pkg._lib.LIB_PATH, foreign)
-    assert _child(REFUSAL.format(root=ABI.ROOT), dict(os.environ, SLAMHIP_LIBRARY=foreign)) == ["refused"]
-
-
-def test_the_loader_names_the_build_command_when_the_library_was_not_built(pkg, tmp_path):
-    copy = tmp_path / "pkg"
-    copy.mkdir()
-    pkgdir = os.path.dirname(os.path.abspath(pkg._lib.__file__))
-    for path in glob.glob(os.path.join(pkgdir, "*.py")) + [os.path.join(pkgdir, "libslamhip.so")]:
-        shutil.copy(path, str(copy))
-    env = {k: v for k, v in os.environ.items() if k != "SLAMHIP_LIBRARY"}
-    assert _child(MISSING.format(copy=str(copy)), env) == ["missing"]

@@ -1,14 +1,11 @@
 """FastSLAM 2.0 with unknown correspondences (slam_pf_step_proposal_unknown / slam_pf_associate_proposal,
 include/ext/slamhip_proposal.h), the parts that need no GPU: tests/proposal_unknown_ref.py against the oracle's predict,
-update_unknown and step_proposal; the conditions of the scene the GPU test runs; the surface checks tests/test_linear_ref_cpu.py
-makes for its extension library, here for this one; and the status codes that are decided before a device is touched."""
+update_unknown and step_proposal; the conditions of the scene the GPU test runs; what is particular to this library's surface (the
+checks every side library shares are made from its row of the table by tests/test_companions_cpu.py); and the status codes that
+are decided before a device is touched."""
 import ctypes
-import glob
 import math
 import os
-import shutil
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -120,58 +117,18 @@ def test_a_ninth_landmark_exhausts_the_slots_and_is_reported_dropped():
     assert (pf.last_nis[dec[-1] < 0] != pf.last_nis[dec[-1] < 0]).all() and np.isfinite(pf.last_nis[dec[-1] >= 0]).all()
 
 
-# ---- the surface ----------------------------------------------------------------------------------------------------------------------
-def test_header_ctypes_library_and_julia_name_the_same_surface(pkg):
+# ---- the surface: the checks every library shares are tests/test_companions_cpu.py's, from this library's row of the table --------------
+def test_what_is_particular_to_this_library(pkg):
     L = pkg._lib
-    loader = L.proposal_lib
-    sigs = L.PROPOSAL_SIGNATURES
-    assert loader.signatures is sigs and loader.name == "proposal"
-    assert loader.path == L.PROPOSAL_LIB_PATH == os.path.join(os.path.dirname(L.LIB_PATH), "libslamhip_proposal.so")
-    names = ABI.declared(HEADER)
-    assert names == NAMES == set(sigs) == ABI.exported(loader.path), (names, set(sigs), ABI.exported(loader.path))
-    protos = ABI.prototypes(HEADER)
-    assert set(protos) == names
-    for sym, (res, args) in sigs.items():
-        assert protos[sym] == len(args), (sym, protos[sym], len(args))
-        assert res is ctypes.c_int, sym
-    needed = ABI.dynamic_section(loader.path)
-    assert "libslamhip.so" in needed and "$ORIGIN" in needed
-    libs = {line.split("[")[1].split("]")[0] for line in needed.splitlines() if "(NEEDED)" in line}
-    system = ("libstdc++", "libm.", "libgcc_s", "libc.", "libdl", "libpthread", "librt", "ld-linux")
-    assert {x for x in libs if not x.startswith(system)} == {"libslamhip.so"} | {x for x in libs if x.startswith("libamdhip64")}
-    assert any(x.startswith("libamdhip64") for x in libs)
-    ldd = subprocess.run(["ldd", loader.path], capture_output=True, text=True).stdout
-    assert "libslamhip.so" in ldd and "torch" not in ldd and "python" not in ldd
-    lib = loader()
-    assert lib is loader() and all(getattr(lib, sym).argtypes == args for sym, (_res, args) in sigs.items())
-    calls = ABI.julia_ccalls("libslamhip_proposal")
-    assert {c[0] for c in calls} == names
-    for sym, ret, nargs in calls:
-        assert ret == "Cint" and nargs == len(sigs[sym][1]), (sym, ret, nargs, len(sigs[sym][1]))
+    assert NAMES == set(L.proposal_lib.signatures)
     with open(ABI.JULIA) as f:
         src = f.read()
-    assert "SLAMHIP_PROPOSAL_LIB" in src
     for word in ("step_proposal_unknown!", "associate_proposal", "proposal_max_obs"):
         assert word in src.split("module SLAMHip")[1].split("const libslamhip =")[0], word      # exported
     with open(HEADER) as f:
         text = f.read()
     assert '#include "slamhip.h"' in text and "#define SLAM_PF_PROPOSAL_MAXOBS 16" in text
     assert L.proposal_max_obs() == 16 == P.MAXOBS                       # (slam_pf_proposal_limits needs no device)
-
-
-def test_the_tables_are_unchanged_and_the_export_sets_disjoint(pkg):
-    L = pkg._lib
-    assert list(L.COMPANIONS) == ["frame", "join", "evidence", "jc", "path", "copy", "handover", "pfcopy"]
-    assert list(L.EXTENSIONS) == ["factor"]
-    assert L.proposal_lib not in list(L.COMPANIONS.values()) + list(L.EXTENSIONS.values())
-    mine = ABI.exported(L.PROPOSAL_LIB_PATH)
-    assert mine == NAMES
-    assert not mine & ABI.exported(L.LIB_PATH)
-    assert not NAMES & set(L.SIGNATURES)
-    for name, c in list(L.COMPANIONS.items()) + list(L.EXTENSIONS.items()) + [("linear", L.linear_lib)]:
-        assert not mine & ABI.exported(c.path), name
-        assert not NAMES & set(c.signatures), name
-    assert HEADER not in glob.glob(os.path.join(ABI.INCLUDE, "slamhip*.h"))
     for word in ("step_proposal_unknown", "associate_proposal"):
         assert callable(getattr(pkg.pf.PFShard, word)), word
 
@@ -210,62 +167,3 @@ def test_bad_arguments_are_status_codes_without_a_device(pkg):
     assert lib.slam_pf_proposal_limits(None) == BAD
     lim = (ctypes.c_int * 4)(9, 9, 9, 9)
     assert lib.slam_pf_proposal_limits(lim) == 0 and list(lim) == [16, 0, 0, 0]
-
-
-REFUSAL = """
-import os, sys
-sys.path.insert(0, {root!r})
-from __graft_entry__ import load_package
-L = load_package()._lib
-assert L.LIB_PATH == os.environ["SLAMHIP_LIBRARY"]
-own = os.path.join(os.path.dirname(os.path.abspath(L.__file__)), "libslamhip.so")
-try:
-    L.proposal_lib()
-except ImportError as e:
-    for word in ("libslamhip_proposal.so", own, L.LIB_PATH, "SLAMHIP_LIBRARY"):
-        assert word in str(e), (word, str(e))
-else:
-    raise SystemExit("opened although the handles belong to another library")
-print("refused")
-"""
-
-MISSING = """
-import importlib.util, os, sys
-d = {copy!r}
-spec = importlib.util.spec_from_file_location("slam_copy_without_proposal", os.path.join(d, "__init__.py"), submodule_search_locations=[d])
-mod = importlib.util.module_from_spec(spec)
-sys.modules[spec.name] = mod
-spec.loader.exec_module(mod)
-loader = mod._lib.proposal_lib
-assert loader.path == os.path.join(d, "libslamhip_proposal.so") and not os.path.exists(loader.path)
-try:
-    loader()
-except ImportError as e:
-    for word in (loader.path, "is missing", "make -C slam.jl_amd/csrc"):
-        assert word in str(e), (word, str(e))
-else:
-    raise SystemExit("opened although it is not there")
-print("missing")
-"""
-
-
-def _child(script, env):
-    res = subprocess.run([sys.executable, "-c", script], capture_output=True, text=True, timeout=300, env=env)
-    assert res.returncode == 0, res.stdout + res.stderr
-    return res.stdout.split()
-
-
-def test_the_loader_refuses_a_foreign_product_library(pkg, tmp_path):
-    foreign = str(tmp_path / "libslamhip.so")
-    shutil.copy(pkg._lib.LIB_PATH, foreign)
-    assert _child(REFUSAL.format(root=ABI.ROOT), dict(os.environ, SLAMHIP_LIBRARY=foreign)) == ["refused"]
-
-
-def test_the_loader_names_the_build_command_when_the_library_was_not_built(pkg, tmp_path):
-    copy = tmp_path / "pkg"
-    copy.mkdir()
-    pkgdir = os.path.dirname(os.path.abspath(pkg._lib.__file__))
-    for path in glob.glob(os.path.join(pkgdir, "*.py")) + [os.path.join(pkgdir, "libslamhip.so")]:
-        shutil.copy(path, str(copy))
-    env = {k: v for k, v in os.environ.items() if k != "SLAMHIP_LIBRARY"}
-    assert _child(MISSING.format(copy=str(copy)), env) == ["missing"]

@@ -1,17 +1,16 @@
 """The joint update of up to 64 observations (libslamhip_wide.so, include/ext/slamhip_wide.h), the parts that need no GPU:
 tests/wide_ref.py against tests/fej_ref.py (m <= 8: the same rule) and against the oracle (the points re-set to x); H N = 0 for the
 wide H; that the joint update and the chain of 8-observation batches are DIFFERENT filters; the condition of the scenes the GPU
-tests use; failing pivots at m > 8; and the surface checks tests/test_fej_ref_cpu.py makes for its library, here for this one.
+tests use; failing pivots at m > 8; and what is particular to this library's surface (the checks every side library shares are
+made from its row of the table by tests/test_companions_cpu.py).
 
 The bars: 1e-12 where fp64 rounding alone separates two quantities (two NumPy evaluations of the same rule on matrices of
 condition <= 1e5).  The scenes: positive definite in the reference for both dtypes' rounded states and both seeds, cond(S) <= 2e6
 (the double front half then carries cond(S) u64 = 2e-10, below the fp64 bar 1e-9 of the GPU tests), the smallest l_ii >= 0.010."""
 import ctypes
-import glob
 import inspect
 import math
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -122,35 +121,14 @@ def test_a_failing_pivot_and_coinciding_points_change_nothing_at_twenty_observat
 
 
 # ---- 4. the surface -----------------------------------------------------------------------------------------------------------------
-def test_header_ctypes_library_and_julia_name_the_same_surface(pkg):
+def test_what_is_particular_to_this_library(pkg):
+    """The checks every library shares are tests/test_companions_cpu.py's, from this library's row of the table (that it is linked
+    against the product library only, not against libslamhip_fej.so, among them)."""
     L = pkg._lib
-    loader = L.wide_lib
-    sigs = L.WIDE_SIGNATURES
-    assert loader.signatures is sigs and loader.name == "wide"
-    assert loader.path == L.WIDE_LIB_PATH == os.path.join(os.path.dirname(L.LIB_PATH), "libslamhip_wide.so")
-    names = ABI.declared(HEADER)
     assert len(NAMES) == 3
-    assert names == NAMES == set(sigs) == ABI.exported(loader.path), (names, set(sigs), ABI.exported(loader.path))
-    protos = ABI.prototypes(HEADER)
-    assert set(protos) == names
-    for sym, (res, args) in sigs.items():
-        assert protos[sym] == len(args), (sym, protos[sym], len(args))
-        assert res is ctypes.c_int, sym
-    needed = ABI.dynamic_section(loader.path)
-    assert "libslamhip.so" in needed and "$ORIGIN" in needed and "libslamhip_fej" not in needed      # the product library only
-    ldd = subprocess.run(["ldd", loader.path], capture_output=True, text=True).stdout
-    assert "libslamhip.so" in ldd and "libslamhip_fej" not in ldd and "torch" not in ldd and "python" not in ldd
-    lib = loader()
-    assert lib is loader() and all(getattr(lib, sym).argtypes == args for sym, (_res, args) in sigs.items())
-    calls = ABI.julia_ccalls("libslamhip_wide")
-    assert {c[0] for c in calls} == names
-    for sym, ret, nargs in calls:
-        assert ret == "Cint" and nargs == len(sigs[sym][1]), (sym, ret, nargs, len(sigs[sym][1]))
+    assert NAMES == set(L.wide_lib.signatures)
     with open(ABI.JULIA) as f:
         src = f.read()
-    for sym in names:
-        assert f"(:{sym}, libslamhip_wide)" in src
-    assert "SLAMHIP_WIDE_LIB" in src
     for word in ("update_joint!", "joint_nis", "wide_limits"):
         assert word in src.split("module SLAMHip")[1].split("const libslamhip =")[0], word      # exported
     with open(HEADER) as f:
@@ -158,25 +136,8 @@ def test_header_ctypes_library_and_julia_name_the_same_surface(pkg):
     assert '#include "slamhip_fej.h"' in text
     assert L.SLAM_WIDE_MAXOBS == 64 == W.MAXOBS and "#define SLAM_WIDE_MAXOBS 64" in text
     lim = (ctypes.c_int32 * 1)()
-    assert lib.slam_ekf_wide_limits(lim) == L.SLAM_OK and list(lim) == [64]      # (touches no device)
-
-
-def test_the_tables_are_unchanged_and_every_other_export_set_is_what_it_was(pkg):
-    L = pkg._lib
-    assert list(L.COMPANIONS) == ["frame", "join", "evidence", "jc", "path", "copy", "handover", "pfcopy"]
-    assert list(L.EXTENSIONS) == ["factor"]
-    assert L.wide_lib not in list(L.COMPANIONS.values()) + list(L.EXTENSIONS.values())
-    mine = ABI.exported(L.WIDE_LIB_PATH)
-    assert mine == NAMES
-    assert not NAMES & set(L.SIGNATURES)
-    product = ABI.declared(os.path.join(ABI.INCLUDE, "slamhip.h")) | ABI.declared(os.path.join(ABI.INCLUDE, "slamhip_diag.h"))
-    assert ABI.exported(L.LIB_PATH) == product == set(L.SIGNATURES)
-    others = [("linear", L.linear_lib), ("proposal", L.proposal_lib), ("local", L.local_lib), ("iterated", L.iterated_lib), ("fej", L.fej_lib)]
-    for name, c in list(L.COMPANIONS.items()) + list(L.EXTENSIONS.items()) + others:
-        assert ABI.exported(c.path) == set(c.signatures), name            # every other library exports what its table lists ...
-        assert not mine & set(c.signatures), name                         # ... and none of this library's names
+    assert L.wide_lib().slam_ekf_wide_limits(lim) == L.SLAM_OK and list(lim) == [64]      # (touches no device)
     assert ABI.exported(L.FEJ_LIB_PATH) == FEJ_NAMES and len(FEJ_NAMES) == 11      # moving the object's layout added no export there
-    assert HEADER not in glob.glob(os.path.join(ABI.INCLUDE, "slamhip*.h"))
     for word in ("update_joint", "joint_nis"):
         assert callable(getattr(pkg.FirstEstimates, word)), word
     assert callable(pkg.EKFSlamState.update_joint_at_estimates)
